@@ -4,7 +4,20 @@
 BASELINE.json metric: "ms/iter + effective TFLOP/s, tp_columnwise AG+GEMM m=65536 bf16 at
 1/2/4/8 GPUs". n=k=1024 is the reference README's m=65536 example (``README.md:37-39``).
 
-Contract (driver):  python bench.py --gpus N --steps K --warmup W
+Contract (driver):  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+  * a plain run does what the headline needs and nothing else: set up, pre-warm, W warmups, K
+    timed steps, the JSON line. At one GPU the step is the GEMM front-end's own kernel choice
+    (``gemm (world=1)/auto``), with no search; at N>1 the preflight and the autotuner still pick
+    the plan (they decide what the headline times). ``--full`` adds everything measured or
+    checked beside it: the search over the kernel families at one GPU, the vendor-library slots
+    (``vendor_ms``), the fp32 reference check of the timed run (``valid``, ``max_err``), the
+    reference-default timing (``harness_mean_ms``) and the N>1 diagnostics (``diag``). Without
+    it those fields are null / empty;
+  * ``--dump-outputs DIR``: after the timed steps rank 0 writes the result of the LAST timed
+    step, the [m, n] tensor ``run()`` returns, as ``DIR/out.npy`` (float32). A result over the
+    size budget (``DUMP_BYTES``) is cut to a fixed, seeded sample of whole rows, in row order.
+    The inputs are drawn from a seeded generator (seed 42), so the same arguments give the same
+    inputs, and the same sample, in every run and every build;
   * N>1 is launched by torch.distributed.run, one rank per GPU (RANK/LOCAL_RANK/WORLD_SIZE env);
     started without a launcher, ``--gpus N`` runs torch.distributed.run itself as a child
     process and relays rank 0's line (``self_launch``);
@@ -37,8 +50,9 @@ to the next fastest if it fails there). The whole job runs against ONE wall-cloc
 timeout is cut to what is left, so a node where candidates hang still reports inside it.
 Every rank issues the same number of run() calls (the pre-warm count is MAX-reduced), as each
 call holds collectives / epoch-matched signals. Synthetic U[-1,1) inputs of the named shape (no
-datasets exist offline); the result is validated against an fp32 reference, with the
-reference's rule (atol = 1e-3 k) and a tight internal bound (max|err| <= 2^-7 max|ref| + k 2^-12).
+datasets exist offline); tuning runs, and under ``--full`` the timed run, are validated against
+an fp32 reference, with the reference's rule (atol = 1e-3 k) and a tight internal bound
+(max|err| <= 2^-7 max|ref| + k 2^-12).
 """
 
 from __future__ import annotations
@@ -286,6 +300,42 @@ def harness_times(impl, comm, iters: int):
     return [float(x) for x in t.cpu()]
 
 
+DUMP_BYTES = 32 << 20  # budget of one --dump-outputs directory (all arrays together)
+DUMP_SEED = 0
+
+
+def dump_outputs(path: str, arrays: dict) -> dict:
+    """Write each tensor of ``arrays`` as ``path/<name>.npy`` (float32; float64 and integer
+    results as float64). An array over its share of ``DUMP_BYTES`` is sampled, the same way in
+    every run: whole rows drawn once from a seeded generator and kept in row order (every column
+    of a kept row), or single elements of the flattened array where one row alone is too large.
+    Returns {name: [shape written, shape of the full result]}."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1)
+    rng = np.random.default_rng(DUMP_SEED)
+    done = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        wide = t.dtype in (torch.float64, torch.int32, torch.int64)
+        esz = 8 if wide else 4
+        full = list(t.shape)
+        if t.numel() * esz > share:
+            row = (t.numel() // t.shape[0]) * esz if t.dim() >= 2 else share + 1
+            if row <= share:
+                keep = np.sort(rng.choice(t.shape[0], share // row, replace=False))
+            else:
+                t = t.reshape(-1)
+                keep = np.sort(rng.choice(t.shape[0], share // esz, replace=False))
+            t = t.index_select(0, torch.from_numpy(keep).to(t.device))
+        arr = t.to(torch.float64 if wide else torch.float32).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), arr)
+        done[name] = [list(arr.shape), full]
+    return done
+
+
 def child_main(a) -> int:
     """One measurement on this rank's GPU; writes a JSON result file (rank 0 aggregates)."""
     import torch
@@ -329,6 +379,8 @@ def child_main(a) -> int:
         # timed step must validate too (cross-rank ordering bugs show up under back-to-back
         # epochs, not on the first, isolated run)
         impl.check_health()
+        if a.dump_outputs and comm.rank == 0:
+            res["dumped"] = dump_outputs(a.dump_outputs, {"out": out})
         if a.validate and valid:
             valid = _check(impl, out, res)
         if a.harness_iters > 0:
@@ -500,12 +552,15 @@ class Job:
         return out, status, proc.returncode, timeout
 
     def measure(self, impl: str, opts: dict, steps: int, warmup: int, validate: bool,
-                timeout: float, prewarm_ms: float = 0.0, harness_iters: int = 0) -> dict:
-        """Run one measurement in a child per rank; every rank returns the same dict."""
+                timeout: float, prewarm_ms: float = 0.0, harness_iters: int = 0,
+                dump_outputs: str = "") -> dict:
+        """Run one measurement in a child per rank; every rank returns the same dict.
+        ``dump_outputs``: rank 0's child writes the last timed step's result there."""
         extra = ["--steps", str(steps), "--warmup", str(warmup), "--prewarm-ms",
                  str(prewarm_ms), "--harness-iters", str(harness_iters)]
-        if validate:
-            extra.append("--validate")
+        extra.append("--validate" if validate else "--no-validate")
+        if dump_outputs:
+            extra += ["--dump-outputs", os.path.abspath(dump_outputs)]
         out, status, rc, timeout = self._spawn(impl, opts, timeout, extra)
         if status == "timeout":
             local = {"ok": False, "error": f"timeout after {timeout:.0f}s"}
@@ -532,6 +587,8 @@ class Job:
             hm = [r["harness_mean_ms"] for r in results if "harness_mean_ms" in r]
             if hm:
                 res["harness_mean_ms"] = max(hm)
+            if results[0].get("dumped"):
+                res["dumped"] = results[0]["dumped"]
             return res
         errs = [r.get("error") for r in results if not r.get("ok")]
         return {"ok": False, "error": errs[0] if errs else "unknown"}
@@ -692,8 +749,11 @@ def final_measure(job, chosen, fallbacks, a, tune: dict):
             break
         t0 = time.time()
         timeout = min(a.candidate_timeout + a.steps * 0.05 + a.harness_iters * 0.05, room)
-        r = job.measure(cand[1], cand[2], a.steps, a.warmup, a.validate, timeout,
-                        prewarm_ms=a.prewarm_ms, harness_iters=a.harness_iters)
+        dump = getattr(a, "dump_outputs", "")
+        r = job.measure(cand[1], cand[2], a.steps, a.warmup,
+                        getattr(a, "validate_final", a.validate), timeout,
+                        prewarm_ms=a.prewarm_ms, harness_iters=a.harness_iters,
+                        **({"dump_outputs": dump} if dump else {}))
         job.log(f"final {cand[0]}: {r.get('ms', r.get('error'))} valid={r.get('valid')} "
                 f"({time.time() - t0:.1f} s)")
         if r["ok"] and r.get("valid") is not False:
@@ -787,7 +847,15 @@ def main(argv=None) -> int:
     p.add_argument("--harness-iters", type=int, default=-1,
                    help="iterations of the reference-default timing (barrier before each, "
                         "MAX over ranks) after the timed window -> harness_mean_ms "
-                        "(-1 = --steps, 0 = off)")
+                        "(-1 = --steps with --full, off without; 0 = off)")
+    p.add_argument("--full", action="store_true",
+                   help="everything beside the headline: autotune over the kernel families at "
+                        "world 1, the vendor-library slots (vendor_ms), the fp32 reference "
+                        "check of the timed run (valid, max_err), the reference-default timing "
+                        "(harness_mean_ms) and, at world > 1, the first-contact diagnostics")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write the result of the last one (rank 0's; a "
+                        "fixed seeded sample of rows when it is large) as DIR/out.npy, float32")
     # child-mode arguments (internal)
     p.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     p.add_argument("--child-out", help=argparse.SUPPRESS)
@@ -797,7 +865,10 @@ def main(argv=None) -> int:
     p.add_argument("--validate", dest="validate", action="store_true", help=argparse.SUPPRESS)
     a = p.parse_args(argv)
     if a.harness_iters < 0:
-        a.harness_iters = a.steps
+        a.harness_iters = a.steps if a.full else 0
+    # the fp32 reference check of the timed run belongs to --full; tuning (world > 1, or
+    # --candidates) always validates: there the check decides which plan the headline times
+    a.validate_final = a.validate and a.full
     if a.child:
         if a.child_impl.startswith("preflight_"):
             return preflight_child(a)
@@ -847,6 +918,10 @@ def main(argv=None) -> int:
             raise SystemExit(f"unknown --algorithm {a.algorithm}; choose from "
                              f"{[c[0] for c in every]}")
         chosen = match[0]
+    elif world == 1 and not a.full and not a.candidates:
+        # one GPU, no search: the GEMM front-end's own choice of kernel ("auto", the first
+        # native slot); the other families and the vendor library are timed under --full
+        chosen = [c for c in pool if c[1] == "native"][0]
     else:
         picked = autotune(job, pool, a, world, tune, pre)
         if picked is None:
@@ -858,7 +933,7 @@ def main(argv=None) -> int:
         sys.stderr.write(f"final measurement failed (autotune: {json.dumps(tune)})\n")
         return 1
     diag = None
-    if a.diagnose == "on" or (a.diagnose == "auto" and world > 1):
+    if a.diagnose == "on" or (a.diagnose == "auto" and world > 1 and a.full):
         # bounded: the measurements' own budget plus child start-up, and never past the deadline
         room = job.left() - 5.0
         if job.bcast(room < a.diag_budget_s + 15.0 if job.rank == 0 else None):
@@ -908,6 +983,7 @@ def main(argv=None) -> int:
             "prewarm_ms": a.prewarm_ms,
             "deadline_s": a.deadline_s, "job_wall_s": round(time.time() - job.t_start, 1),
             "autotune_ms": tune,
+            "full": a.full, "outputs": final.get("dumped"),
         }
         if diag is not None:
             line["diag"] = diag

@@ -529,15 +529,44 @@ PINNED = {
     "unroll2": "d2e1ff0",   # r6_38 (flat)
 }
 
+# The pinned revisions' gemm_kernels.h is rebuilt without git history (a shallow or exported
+# checkout has none): research/lab/pinned/ holds a chain of diffs that walks back from the
+# product header (identical to fc1ce0f's) one distinct revision at a time; revisions whose header
+# is byte-identical share a step. The other two headers (gemm.h, tile_map.h) did not change since
+# the oldest pinned revision and come from the working tree. Each rebuilt header is checked
+# against the sha256 of the text that was measured, so an edit of the product header that the
+# chain no longer fits fails loudly (then: re-base pinned/1_*.diff on the new product header).
+CHAIN = ["fc1ce0f", "cb084d4", "e2c6c5f", "34f0106", "38ab6ea", "2c4e4ca"]  # newest first
+SAME_AS = {"b8b30bb": "34f0106", "8c58daa": "34f0106", "d2e1ff0": "fc1ce0f"}
+SHA256 = {"fc1ce0f": "dcc3f42196ae3f21", "cb084d4": "069e0c68d325214b",
+          "e2c6c5f": "dad98a5e8633ae95", "34f0106": "420c39d05549ebc9",
+          "38ab6ea": "b911949eb74c2f17", "2c4e4ca": "a30b9a41c45d6f00"}
+
+
+def pinned_header(rev: str) -> str:
+    """gemm_kernels.h as committed at a pinned revision (see CHAIN)."""
+    import hashlib
+
+    rev = SAME_AS.get(rev, rev)
+    text = open(os.path.join(CSRC, "gemm_kernels.h")).read()
+    for i, step in enumerate(CHAIN[1:CHAIN.index(rev) + 1], 1):
+        text = _apply_diff(text, os.path.join("pinned", f"{i}_{step}.diff"), exact=True)
+    if hashlib.sha256(text.encode()).hexdigest()[:16] != SHA256[rev]:
+        raise RuntimeError(f"pinned revision {rev}: the rebuilt gemm_kernels.h is not the "
+                           "measured text (the product header moved on: re-base "
+                           "research/lab/pinned/1_*.diff)")
+    return text
+
 
 def source(name: str, variant: str) -> str:
     """A header of csrc/gemm: from the working tree; for the ``ref`` variant from git revision
     ``DDLB_LAB_REF`` (default HEAD), so an edited kernel is timed against the committed one in
-    the same process; for a PINNED variant from its revision."""
-    rev = REF_REV if variant == "ref" else PINNED.get(variant)
-    if rev is None:
+    the same process; for a PINNED variant, gemm_kernels.h of its revision."""
+    if variant != "ref" and variant in PINNED and name == "gemm_kernels.h":
+        return pinned_header(PINNED[variant])
+    if variant != "ref":
         return open(os.path.join(CSRC, name)).read()
-    return subprocess.run(["git", "-C", ROOT, "show", f"{rev}:csrc/gemm/{name}"],
+    return subprocess.run(["git", "-C", ROOT, "show", f"{REF_REV}:csrc/gemm/{name}"],
                           capture_output=True, text=True, check=True).stdout
 
 
@@ -549,14 +578,15 @@ DIFFS = {  # variants kept as a diff against the product header (research/lab/<f
 }
 
 
-def _apply_diff(text: str, diff_name: str) -> str:
+def _apply_diff(text: str, diff_name: str, exact: bool = False) -> str:
     import tempfile
 
     with tempfile.TemporaryDirectory() as td:
         os.makedirs(os.path.join(td, "csrc", "gemm"))
         with open(os.path.join(td, "csrc", "gemm", "gemm_kernels.h"), "w") as f:
             f.write(text)
-        r = subprocess.run(["patch", "-p1", "-s", "-i", os.path.join(HERE, diff_name)],
+        r = subprocess.run(["patch", "-p1", "-s", *(["-F0"] if exact else []), "-i",
+                            os.path.join(HERE, diff_name)],
                            cwd=td, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"{diff_name} does not apply: {r.stdout}{r.stderr}")

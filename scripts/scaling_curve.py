@@ -73,7 +73,8 @@ def _bench_row(obj: dict) -> dict:
             "value": float(obj["value"]), "unit": obj.get("unit", ""),
             "scaling": obj.get("scaling", "weak"),
             "algorithm": cfg.get("algorithm", cfg.get("parallelism", "")),
-            "valid": obj.get("valid", True)}
+            # null = not checked (a bench.py run without --full): kept, only a failed check drops
+            "valid": obj.get("valid") is not False}
 
 
 def parse_csv(path: str) -> List[dict]:

@@ -9,6 +9,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARGS = ["--steps", "3", "--warmup", "1", "-m", "256", "-n", "64", "-k", "64",
         "--algorithm", "pytorch(rccl+hipblaslt)", "--dtype", "float32"]
+FULL = ARGS + ["--full"]  # the reference check, harness timing and diagnostics live behind it
 
 
 def _json_line(out: str):
@@ -26,7 +27,7 @@ def _env():
 
 
 def test_bench_world1_cpu():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *ARGS],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *FULL],
                        capture_output=True, text=True, timeout=300, env=_env())
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
@@ -44,7 +45,7 @@ def test_bench_world2_cpu():
 
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", *ARGS]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", *FULL]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=_env())
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     d = _json_line(r.stdout)
@@ -56,7 +57,7 @@ def test_bench_gpus2_without_launcher_cpu():
     """``--gpus 2`` started as a plain ``python bench.py`` (no WORLD_SIZE): bench.py runs
     torch.distributed.run itself as a child and relays exactly one JSON line (the driver's N>1
     record must not depend on how it launches the script)."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", *ARGS],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", *FULL],
                        capture_output=True, text=True, timeout=400, env=_env())
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     d = _json_line(r.stdout)
@@ -111,7 +112,8 @@ def test_bench_rowwise_world2_cpu():
     from conftest import free_port
 
     args = ["--steps", "3", "--warmup", "1", "-m", "256", "-n", "64", "-k", "64", "--dtype",
-            "float32", "--primitive", "tp_rowwise", "--algorithm", "row/pytorch(rccl+hipblaslt)"]
+            "float32", "--primitive", "tp_rowwise", "--algorithm", "row/pytorch(rccl+hipblaslt)",
+            "--full"]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", *args]
@@ -299,7 +301,7 @@ def test_bench_world2_cpu_preflight_fields():
                                              "ipc": "failed: scripted"})
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", *ARGS]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", *FULL]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=env)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     d = _json_line(r.stdout)
@@ -446,3 +448,68 @@ def test_diagnose_message_sizes():
     assert sz["rs_block"] == 2048 * 8192 * 2
     per = diagnose.merge_ranks([{"rccl": {"x": 1}, "xgmi": {"a": 1}}, {"xgmi": {"a": 2}}])
     assert per["rccl"] == {"x": 1} and per["xgmi"] == {"0": {"a": 1}, "1": {"a": 2}}
+
+
+def _bench(args, env=None):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args],
+                       capture_output=True, text=True, timeout=300, env=env or _env())
+    assert r.returncode == 0, r.stderr[-3000:]
+    return _json_line(r.stdout)
+
+
+def test_plain_run_is_lean_and_dumps_the_same_outputs(tmp_path):
+    """A plain run reports the headline only (no reference check, no harness timing, no vendor
+    slots, no search) and --dump-outputs writes the last timed step's result: float32, the full
+    [m, n] at this size, the product of the seeded inputs, identical from a plain and a --full
+    run (same arguments, same inputs)."""
+    import numpy as np
+    import torch
+
+    from ddlb_amd.primitives.base import uniform_pm1
+
+    plain = _bench([*ARGS, "--dump-outputs", str(tmp_path / "plain")])
+    assert plain["steps"] == 3 and plain["ms_per_step"] > 0 and plain["full"] is False
+    assert plain["valid"] is None and plain["harness_mean_ms"] is None
+    assert plain["max_err"] is None and plain["vendor_ms"] == {} and plain["autotune_ms"] == {}
+    assert "diag" not in plain
+    assert plain["outputs"] == {"out": [[256, 64], [256, 64]]}
+    full = _bench([*FULL, "--dump-outputs", str(tmp_path / "full")])
+    assert full["valid"] is True and full["harness_mean_ms"] > 0 and full["full"] is True
+    for key in ("metric", "unit", "higher_is_better", "dtype"):
+        assert plain[key] == full[key]
+    a, b = np.load(tmp_path / "plain" / "out.npy"), np.load(tmp_path / "full" / "out.npy")
+    assert a.dtype == np.float32 and a.shape == (256, 64)
+    assert np.array_equal(a, b)
+    g = torch.Generator().manual_seed(42)  # the primitive's inputs: A [m, k], then B [k, n]
+    A = uniform_pm1((256, 64), "float32", g, "cpu")
+    B = uniform_pm1((64, 64), "float32", g, "cpu")
+    assert np.abs(a - (A.double() @ B.double()).numpy()).max() <= 64 * 2.0 ** -20
+
+
+def test_dump_outputs_samples_large_results(tmp_path, monkeypatch):
+    """Over the size budget the dump keeps whole rows, drawn once from a seeded generator, in
+    row order: the same rows in every call, inside the budget; one over-long row falls back to
+    elements of the flattened result. float64 / integer results are written as float64."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4096)
+    t = torch.arange(1000 * 16, dtype=torch.float32).reshape(1000, 16).to(torch.bfloat16)
+    done = bench.dump_outputs(str(tmp_path / "a"), {"out": t})
+    bench.dump_outputs(str(tmp_path / "b"), {"out": t})
+    a, b = np.load(tmp_path / "a" / "out.npy"), np.load(tmp_path / "b" / "out.npy")
+    assert done == {"out": [[64, 16], [1000, 16]]}
+    assert a.dtype == np.float32 and a.shape == (64, 16) and a.nbytes <= 4096
+    assert np.array_equal(a, b)
+    rows = np.random.default_rng(bench.DUMP_SEED).choice(1000, 64, replace=False)
+    assert np.array_equal(a, t.float().numpy()[np.sort(rows)])
+    wide = torch.arange(2 * 4096, dtype=torch.int64).reshape(2, 4096)
+    bench.dump_outputs(str(tmp_path / "c"), {"out": wide})
+    c = np.load(tmp_path / "c" / "out.npy")
+    assert c.dtype == np.float64 and c.shape == (512,) and np.all(np.diff(c) > 0)
+    small = torch.ones(3, 5, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "d"), {"out": small})
+    assert np.load(tmp_path / "d" / "out.npy").dtype == np.float64
