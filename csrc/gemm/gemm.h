@@ -27,6 +27,56 @@ enum Tile : int { TILE_AUTO = 0, TILE_256x256 = 1, TILE_256x128 = 2, TILE_128x25
                   TILE_PT8 = 17,      // PT8: persistent T8 (tiles streamed, C stores spread)
                   TILE_T4 = 18,       // T4: 2-phase ping-pong (32 MFMAs per section)
                   TILE_PT4 = 19 };    // PT4: persistent T4
+// What each live code runs: the tile it covers and the tiled kernel's wave grid (wm x wn waves)
+// and DMA interleave. The ping-pong codes (T8 .. PT4) run their own 256x256 kernels on whole
+// tiles; their entry is the tiled kernel that takes every other shape (the interleaved 256x256).
+// The block-scaled MX kernels use the same shapes, never interleaved.
+struct TileCfg { int code, rows, cols, wm, wn; bool ilv; };
+constexpr TileCfg kTileCfgs[] = {
+    {TILE_256x256, 256, 256, 2, 4, false},    {TILE_256x128, 256, 128, 4, 2, false},
+    {TILE_128x256, 128, 256, 2, 4, false},    {TILE_128x128, 128, 128, 2, 2, false},
+    {TILE_256x256_W4, 256, 256, 2, 2, false}, {TILE_256x128_W4, 256, 128, 2, 2, false},
+    {TILE_I256, 256, 256, 2, 4, true},        {TILE_I128, 128, 128, 2, 2, true},
+    {TILE_I256W4, 256, 256, 2, 2, true},      {TILE_T8, 256, 256, 2, 4, true},
+    {TILE_PT8, 256, 256, 2, 4, true},         {TILE_T4, 256, 256, 2, 4, true},
+    {TILE_PT4, 256, 256, 2, 4, true}};
+constexpr int kNumTileCfgs = sizeof(kTileCfgs) / sizeof(kTileCfgs[0]);
+// Index of a tile code in kTileCfgs; -1 for TILE_AUTO, the retired codes and anything else.
+constexpr int tile_slot(int tile) {
+  for (int i = 0; i < kNumTileCfgs; ++i)
+    if (kTileCfgs[i].code == tile) return i;
+  return -1;
+}
+constexpr int tile_rows_of(int tile) {  // (256 for a code without a kernel, as tile_rows has said)
+  const int i = tile_slot(tile);
+  return i < 0 ? 256 : kTileCfgs[i].rows;
+}
+constexpr int tile_cols_of(int tile) {
+  const int i = tile_slot(tile);
+  return i < 0 ? 256 : kTileCfgs[i].cols;
+}
+
+constexpr bool tile_cfgs_distinct() {
+  for (int i = 0; i < kNumTileCfgs; ++i)
+    for (int j = i + 1; j < kNumTileCfgs; ++j)
+      if (kTileCfgs[i].code == kTileCfgs[j].code) return false;
+  return true;
+}
+// the rows x cols every live code has had since the table was three hand-written copies
+constexpr bool tile_is(int tile, int rows, int cols) {
+  return tile_slot(tile) >= 0 && tile_rows_of(tile) == rows && tile_cols_of(tile) == cols;
+}
+static_assert(kNumTileCfgs == 13 && tile_cfgs_distinct(), "thirteen distinct live tile codes");
+static_assert(tile_is(TILE_256x256, 256, 256) && tile_is(TILE_256x128, 256, 128) &&
+              tile_is(TILE_128x256, 128, 256) && tile_is(TILE_128x128, 128, 128) &&
+              tile_is(TILE_256x256_W4, 256, 256) && tile_is(TILE_256x128_W4, 256, 128) &&
+              tile_is(TILE_I256, 256, 256) && tile_is(TILE_I128, 128, 128) &&
+              tile_is(TILE_I256W4, 256, 256) && tile_is(TILE_T8, 256, 256) &&
+              tile_is(TILE_PT8, 256, 256) && tile_is(TILE_T4, 256, 256) &&
+              tile_is(TILE_PT4, 256, 256), "tile_rows / tile_cols per code");
+static_assert(tile_slot(TILE_AUTO) < 0 && tile_slot(5) < 0 && tile_slot(8) < 0 &&
+              tile_slot(9) < 0 && tile_slot(13) < 0 && tile_slot(14) < 0 && tile_slot(15) < 0,
+              "retired codes stay refused");
 // Every mode runs one of this file's hand-written kernels: vendor libraries (hipBLASLt through
 // torch.matmul) are only the comparison baseline of the `pytorch` slot, never behind `native`.
 enum GemmMode : int { GEMM_MODE_AUTO = 0, GEMM_MODE_GENERIC = 1, GEMM_MODE_MX = 2 };

@@ -28,9 +28,11 @@ __device__ __forceinline__ void glds16(const void* g, void* lds) {
   __builtin_amdgcn_global_load_lds((const GLB_AS void*)g, (LDS_AS void*)lds, 16, 0, 0);
 }
 
-// Address of logical A row ``row``: grouped rows, or a per-shard pointer table (direct access).
+// Address of logical A row ``row``: grouped rows, or a per-shard pointer table (direct access;
+// TAB = false compiles the table out).
+template <bool TAB = true>
 __device__ __forceinline__ const char* a_row(const GemmArgs& p, int64_t row, int esz) {
-  if (p.a_table != nullptr) {
+  if (TAB && p.a_table != nullptr) {
     const unsigned ur = (unsigned)row, us = (unsigned)p.shard_rows;
     const unsigned sh = ur / us;
     return (const char*)p.a_table[sh] + (int64_t)(ur - sh * us) * p.lda * esz;
@@ -344,6 +346,9 @@ __device__ __forceinline__ void wait_tile(const GemmArgs& p, int64_t m0, int BM)
 }
 
 // ---------------------------------------------------------------- the tiled kernel
+// Any shape on the fast path (ragged edges: clamped row loads, guarded stores). With MmaMX the
+// compute step is one v_mfma_scale_f32_16x16x128_f8f6f4 per 128-byte K-row (unit E8M0 scales =
+// 127): 2x the bf16 MFMA rate (MI355X_MICROARCH.md "Matrix cores"), same staging.
 template <class Mma, int OUT, int BM, int BN, int WM, int WN, bool ILV = false>
 __global__ __launch_bounds__(WM* WN * 64) void gemm_tn_kernel(const GemmArgs p) {
   constexpr int NT = WM * WN * 64, NW = WM * WN;
@@ -371,7 +376,9 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_tn_kernel(const GemmArgs p) 
     int64_t gr = m0 + row;
     gr = gr < p.M ? gr : p.M - 1;
     const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-    aptr[i] = a_row(p, gr, esz) + chunk * 16;
+    // (the tiled MX kernel reads plain / grouped rows only: gemm_launch sends an A row table with
+    // block-scaled MFMAs to the ping-pong kernels or drops the MX mode)
+    aptr[i] = a_row<!is_pair<Mma>::value>(p, gr, esz) + chunk * 16;
   }
 #pragma unroll
   for (int i = 0; i < LB; ++i) {
@@ -405,22 +412,41 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_tn_kernel(const GemmArgs p) 
   auto compute = [&](int buf) __attribute__((always_inline)) {
     const char* As = smem + buf * STAGE;
     const char* Bs = As + A_BYTES;
+    if constexpr (is_pair<Mma>::value) {  // MX: one scaled MFMA per 128-byte K-row
+      const int c0 = (fq ^ swz) * 16, c1 = ((4 + fq) ^ swz) * 16;
+      auto frag8 = [&](const char* r) __attribute__((always_inline)) {
+        const i32x4 lo = *(const i32x4*)(r + c0), hi = *(const i32x4*)(r + c1);
+        return i32x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+      };
+      i32x8 af[MR], bfr[NR];
 #pragma unroll
-    for (int c4 = 0; c4 < 8; c4 += 4) {
-      const int choff = ((c4 + fq) ^ swz) * 16;
-      i32x4 af[MR], bfr[NR];
+      for (int i = 0; i < MR; ++i) af[i] = frag8(As + (wm * TM + i * 16 + frow) * ROWB);
 #pragma unroll
-      for (int i = 0; i < MR; ++i)
-        af[i] = *(const i32x4*)(As + (wm * TM + i * 16 + frow) * ROWB + choff);
-#pragma unroll
-      for (int j = 0; j < NR; ++j)
-        bfr[j] = *(const i32x4*)(Bs + (wn * TN + j * 16 + frow) * ROWB + choff);
+      for (int j = 0; j < NR; ++j) bfr[j] = frag8(Bs + (wn * TN + j * 16 + frow) * ROWB);
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int i = 0; i < MR; ++i)
 #pragma unroll
-        for (int j = 0; j < NR; ++j) Mma::step(acc[i][j], bfr[j], af[i]);
+        for (int j = 0; j < NR; ++j) Mma::step8(acc[i][j], bfr[j], af[i]);
       __builtin_amdgcn_s_setprio(0);
+    } else {
+#pragma unroll
+      for (int c4 = 0; c4 < 8; c4 += 4) {
+        const int choff = ((c4 + fq) ^ swz) * 16;
+        i32x4 af[MR], bfr[NR];
+#pragma unroll
+        for (int i = 0; i < MR; ++i)
+          af[i] = *(const i32x4*)(As + (wm * TM + i * 16 + frow) * ROWB + choff);
+#pragma unroll
+        for (int j = 0; j < NR; ++j)
+          bfr[j] = *(const i32x4*)(Bs + (wn * TN + j * 16 + frow) * ROWB + choff);
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int i = 0; i < MR; ++i)
+#pragma unroll
+          for (int j = 0; j < NR; ++j) Mma::step(acc[i][j], bfr[j], af[i]);
+        __builtin_amdgcn_s_setprio(0);
+      }
     }
   };
 
@@ -429,50 +455,52 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_tn_kernel(const GemmArgs p) 
   // forming a burst at the top of every K-tile (cdna guide: "the per-phase interleave is the
   // lever"). The DMA writes the other LDS buffer, so it may be placed after this tile's reads.
   auto compute_ilv = [&](int buf, int next_kt) __attribute__((always_inline)) {
-    // First half: MFMAs on the c4=0 fragments, with the next tile's LDS-DMA (1 per PER MFMAs)
-    // and the c4=4 fragment reads (into a second register set) interleaved between them.
-    constexpr int NDMA = LA + LB, NRD = MR + NR, NQ = MR * NR;
-    constexpr int PER = NQ / NDMA > 0 ? NQ / NDMA : 1;
-    const char* As = smem + buf * STAGE;
-    const char* Bs = As + A_BYTES;
-    char* nbase = smem + (buf ^ 1) * STAGE;
-    const int64_t koff = (int64_t)next_kt * ROWB;
-    const int ch0 = ((0 + fq) ^ swz) * 16, ch1 = ((4 + fq) ^ swz) * 16;
-    i32x4 af0[MR], bf0[NR], af1[MR], bf1[NR];
+    if constexpr (ILV) {  // (no interleaved MX kernel: MmaMX has no 16-byte step)
+      // First half: MFMAs on the c4=0 fragments, with the next tile's LDS-DMA (1 per PER MFMAs)
+      // and the c4=4 fragment reads (into a second register set) interleaved between them.
+      constexpr int NDMA = LA + LB, NRD = MR + NR, NQ = MR * NR;
+      constexpr int PER = NQ / NDMA > 0 ? NQ / NDMA : 1;
+      const char* As = smem + buf * STAGE;
+      const char* Bs = As + A_BYTES;
+      char* nbase = smem + (buf ^ 1) * STAGE;
+      const int64_t koff = (int64_t)next_kt * ROWB;
+      const int ch0 = ((0 + fq) ^ swz) * 16, ch1 = ((4 + fq) ^ swz) * 16;
+      i32x4 af0[MR], bf0[NR], af1[MR], bf1[NR];
 #pragma unroll
-    for (int i = 0; i < MR; ++i)
-      af0[i] = *(const i32x4*)(As + (wm * TM + i * 16 + frow) * ROWB + ch0);
+      for (int i = 0; i < MR; ++i)
+        af0[i] = *(const i32x4*)(As + (wm * TM + i * 16 + frow) * ROWB + ch0);
 #pragma unroll
-    for (int j = 0; j < NR; ++j)
-      bf0[j] = *(const i32x4*)(Bs + (wn * TN + j * 16 + frow) * ROWB + ch0);
-    auto rd1 = [&](int r) __attribute__((always_inline)) {
-      if (r < MR) af1[r] = *(const i32x4*)(As + (wm * TM + r * 16 + frow) * ROWB + ch1);
-      else bf1[r - MR] = *(const i32x4*)(Bs + (wn * TN + (r - MR) * 16 + frow) * ROWB + ch1);
-    };
-    auto dma = [&](int d) __attribute__((always_inline)) {
-      if (d < LA) glds16(aptr[d] + koff, nbase + (wave * LA + d) * 1024);
-      else glds16(bptr[d - LA] + koff, nbase + A_BYTES + (wave * LB + d - LA) * 1024);
-    };
-    __builtin_amdgcn_s_setprio(1);
+      for (int j = 0; j < NR; ++j)
+        bf0[j] = *(const i32x4*)(Bs + (wn * TN + j * 16 + frow) * ROWB + ch0);
+      auto rd1 = [&](int r) __attribute__((always_inline)) {
+        if (r < MR) af1[r] = *(const i32x4*)(As + (wm * TM + r * 16 + frow) * ROWB + ch1);
+        else bf1[r - MR] = *(const i32x4*)(Bs + (wn * TN + (r - MR) * 16 + frow) * ROWB + ch1);
+      };
+      auto dma = [&](int d) __attribute__((always_inline)) {
+        if (d < LA) glds16(aptr[d] + koff, nbase + (wave * LA + d) * 1024);
+        else glds16(bptr[d - LA] + koff, nbase + A_BYTES + (wave * LB + d - LA) * 1024);
+      };
+      __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-      Mma::step(acc[q / NR][q % NR], bf0[q % NR], af0[q / NR]);
-      if ((q % PER) == PER - 1) {
-        const int g = q / PER;
-        if (g < NDMA) dma(g);
-        // spread the NRD second-half reads over the NDMA groups
+      for (int q = 0; q < NQ; ++q) {
+        Mma::step(acc[q / NR][q % NR], bf0[q % NR], af0[q / NR]);
+        if ((q % PER) == PER - 1) {
+          const int g = q / PER;
+          if (g < NDMA) dma(g);
+          // spread the NRD second-half reads over the NDMA groups
 #pragma unroll
-        for (int r = (g * NRD) / NDMA; r < ((g + 1) * NRD) / NDMA; ++r) rd1(r);
+          for (int r = (g * NRD) / NDMA; r < ((g + 1) * NRD) / NDMA; ++r) rd1(r);
+        }
       }
+#pragma unroll
+      for (int d = NQ / PER; d < NDMA; ++d) dma(d);
+#pragma unroll
+      for (int r = ((NQ / PER) * NRD) / NDMA; r < NRD; ++r) rd1(r);
+      IlvPattern<0, (NDMA < NQ / PER ? NDMA : NQ / PER), PER, NRD, NDMA>::emit();
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) Mma::step(acc[q / NR][q % NR], bf1[q % NR], af1[q / NR]);
+      __builtin_amdgcn_s_setprio(0);
     }
-#pragma unroll
-    for (int d = NQ / PER; d < NDMA; ++d) dma(d);
-#pragma unroll
-    for (int r = ((NQ / PER) * NRD) / NDMA; r < NRD; ++r) rd1(r);
-    IlvPattern<0, (NDMA < NQ / PER ? NDMA : NQ / PER), PER, NRD, NDMA>::emit();
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) Mma::step(acc[q / NR][q % NR], bf1[q % NR], af1[q / NR]);
-    __builtin_amdgcn_s_setprio(0);
   };
 
   const int nk = p.K * esz / ROWB;
@@ -612,6 +640,35 @@ __device__ __forceinline__ void store8_wt(__amdgpu_buffer_rsrc_t rc, unsigned of
   }
 }
 
+// ---------------------------------------------------------------- ping-pong core (t8, t4, pt8)
+// What the 256x256 ping-pong kernels share (geometry and unit layout: the t8 comment below); each
+// kernel keeps its own schedule, source table, fragment code and C stores. pt4 has its own text
+// (static buffer parity, buffer-descriptor DMA) and takes only t8_perm from here.
+namespace pp {
+constexpr int ROWB = 128, UNIT = 128 * ROWB, STAGE = 4 * UNIT;
+constexpr int UA0 = 0, UA1 = UNIT, UB0 = 2 * UNIT, UB1 = 3 * UNIT;
+}  // namespace pp
+
+__device__ __forceinline__ int t8_perm(int t) { return 8 * ((t & 15) >> 2) + 4 * (t >> 4) + (t & 3); }
+
+__device__ __forceinline__ void pp_bar() {
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+}
+__device__ __forceinline__ void pp_lgkm0() {  // compiler-visible lgkmcnt(0) (see pt4)
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_waitcnt(0xC07F);
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// This wave's slice (rows [16 wave, 16 wave + 16)) of K-tile kt of a unit: 2 x 1 KB LDS-DMA.
+__device__ __forceinline__ void pp_stage(const char* const* src, int kt, char* unit, int wave) {
+  char* dst = unit + wave * 16 * pp::ROWB;
+  glds16(src[0] + (int64_t)kt * pp::ROWB, dst);
+  glds16(src[1] + (int64_t)kt * pp::ROWB, dst + 8 * pp::ROWB);
+}
+
 // ---------------------------------------------------------------- t8: 8-phase ping-pong kernel
 // 256x256 tile, BK = one 128-byte row (64 bf16 / 128 fp8 / 32 f32), 8 waves = 2 groups (wr) x 4
 // (wc), 128x64 per wave as 2x2 quadrants of 64x32 (cdna guide §5 "256^2 8-phase template",
@@ -632,12 +689,9 @@ __device__ __forceinline__ void store8_wt(__amdgpu_buffer_rsrc_t rc, unsigned of
 // 32-row quadrant so a lane's two fragments of a quadrant hold 8 consecutive output columns (one
 // 16-byte store). Measured (profiles/r01/s2/lab/t8_vs_ring2.txt): 1425 TF at 8192^3 (+55 % over
 // the ring kernel, within 2 % of hipBLASLt), +7 % on the 65536x1024x1024 flagship.
-__device__ __forceinline__ int t8_perm(int t) { return 8 * ((t & 15) >> 2) + 4 * (t >> 4) + (t & 3); }
-
 template <class Mma, int OUT>
 __global__ __launch_bounds__(512) void gemm_tn_t8_kernel(const GemmArgs p) {
-  constexpr int ROWB = 128, UNIT = 128 * ROWB, STAGE = 4 * UNIT;
-  constexpr int UA0 = 0, UA1 = UNIT, UB0 = 2 * UNIT, UB1 = 3 * UNIT;
+  using namespace pp;
   __shared__ __attribute__((aligned(1024))) char smem[2 * STAGE];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -668,10 +722,7 @@ __global__ __launch_bounds__(512) void gemm_tn_t8_kernel(const GemmArgs p) {
   }
   wait_tile(p, m0, 256);
   auto stage = [&](const char* const* src, int unit_off, int kt, int buf) __attribute__((always_inline)) {
-    kt = kt < nk ? kt : nk - 1;
-    char* dst = smem + buf * STAGE + unit_off + wave * 16 * ROWB;
-    glds16(src[0] + (int64_t)kt * ROWB, dst);
-    glds16(src[1] + (int64_t)kt * ROWB, dst + 8 * ROWB);
+    pp_stage(src, kt < nk ? kt : nk - 1, smem + buf * STAGE + unit_off, wave);
   };
 
   // ---- fragment reads: unit row base + (lane & 15), logical chunk kk*4 + (lane >> 4)
@@ -739,12 +790,6 @@ __global__ __launch_bounds__(512) void gemm_tn_t8_kernel(const GemmArgs p) {
     }
     __builtin_amdgcn_s_setprio(0);
   };
-#define T8_BAR()                         \
-  do {                                   \
-    __builtin_amdgcn_sched_barrier(0);   \
-    __builtin_amdgcn_s_barrier();        \
-    __builtin_amdgcn_sched_barrier(0);   \
-  } while (0)
 
   // ---- prologue: K-tile 0 whole, UA0 / UB1 of K-tile 1 in flight
   stage(sA[0], UA0, 0, 0);
@@ -754,38 +799,37 @@ __global__ __launch_bounds__(512) void gemm_tn_t8_kernel(const GemmArgs p) {
   stage(sA[0], UA0, 1, 1);
   stage(sB[1], UB1, 1, 1);
   wait_vm<4>();
-  T8_BAR();
+  pp_bar();
   const bool g1 = wr == 1;  // wave-uniform (wave came through readfirstlane)
-  if (g1) T8_BAR();
+  if (g1) pp_bar();
   for (int t = 0; t < nk; ++t) {
     const int b = t & 1, nb = b ^ 1;
     const char* cur = smem + b * STAGE;
     loadA(cur, 0);  // p0
     loadB(cur, 0);
     stage(sA[1], UA1, t + 1, nb);
-    T8_BAR();
+    pp_bar();
     comp(0, 0);
-    T8_BAR();
+    pp_bar();
     loadB(cur, 1);  // p1
     stage(sB[0], UB0, t + 1, nb);
-    T8_BAR();
+    pp_bar();
     comp(0, 1);
-    T8_BAR();
+    pp_bar();
     loadA(cur, 1);  // p2
     stage(sA[0], UA0, t + 2, b);
-    T8_BAR();
+    pp_bar();
     comp(1, 1);
-    T8_BAR();
+    pp_bar();
     loadB(cur, 0);  // p3
     stage(sB[1], UB1, t + 2, b);
     if (g1) wait_vm<4>();
-    T8_BAR();
+    pp_bar();
     comp(1, 0);
     if (!g1) wait_vm<4>();
-    T8_BAR();
+    pp_bar();
   }
-  if (!g1) T8_BAR();
-#undef T8_BAR
+  if (!g1) pp_bar();
   wait_vm<0>();  // never leave an LDS-DMA in flight past the end of the workgroup
 
   // ---- epilogue: a lane holds columns 8*fq .. 8*fq+7 of each 32-column quadrant
@@ -809,8 +853,6 @@ __global__ __launch_bounds__(512) void gemm_tn_t8_kernel(const GemmArgs p) {
   }
 }
 
-
-
 // ---------------------------------------------------------------- t4: 2-phase ping-pong kernel
 // The t8 geometry (256x256 tile, 8 waves in two groups one barrier apart, 16 KB units, 128-byte
 // K rows) with 2 phases per K-tile and 32 MFMAs per compute section, i.e. half the barriers:
@@ -826,8 +868,7 @@ __global__ __launch_bounds__(512) void gemm_tn_t8_kernel(const GemmArgs p) {
 // 8192^3.
 template <class Mma, int OUT, int CMODE = 0>  // CMODE 2: write-through nt C stores (as pt4)
 __global__ __launch_bounds__(512) void gemm_tn_t4_kernel(const GemmArgs p) {
-  constexpr int ROWB = 128, UNIT = 128 * ROWB, STAGE = 4 * UNIT;
-  constexpr int UA0 = 0, UA1 = UNIT, UB0 = 2 * UNIT, UB1 = 3 * UNIT;
+  using namespace pp;
   constexpr bool PAIR = is_pair<Mma>::value;
   __shared__ __attribute__((aligned(1024))) char smem[2 * STAGE];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -859,10 +900,7 @@ __global__ __launch_bounds__(512) void gemm_tn_t4_kernel(const GemmArgs p) {
   wait_tile(p, m0, 256);
   auto stage = [&](const char* const* src, int unit_off, int kt, int buf)
                    __attribute__((always_inline)) {
-    kt = kt < nk ? kt : nk - 1;
-    char* dst = smem + buf * STAGE + unit_off + wave * 16 * ROWB;
-    glds16(src[0] + (int64_t)kt * ROWB, dst);
-    glds16(src[1] + (int64_t)kt * ROWB, dst + 8 * ROWB);
+    pp_stage(src, kt < nk ? kt : nk - 1, smem + buf * STAGE + unit_off, wave);
   };
   const int frow = lane & 15, fq = lane >> 4, sw = (frow >> 1) & 7;
   const int c0 = ((0 + fq) ^ sw) * 16, c1 = ((4 + fq) ^ sw) * 16;
@@ -920,19 +958,6 @@ __global__ __launch_bounds__(512) void gemm_tn_t4_kernel(const GemmArgs p) {
             Mma::step(acc[mq * 4 + f][nq * 2 + g], bR[nq][g][kk], aR[f][kk]);
     }
   };
-#define T4_BAR()                         \
-  do {                                   \
-    __builtin_amdgcn_sched_barrier(0);   \
-    __builtin_amdgcn_s_barrier();        \
-    __builtin_amdgcn_sched_barrier(0);   \
-  } while (0)
-// compiler-visible lgkmcnt(0) (see pt4)
-#define T4_LGKM0()                            \
-  do {                                        \
-    __builtin_amdgcn_sched_barrier(0);        \
-    __builtin_amdgcn_s_waitcnt(0xC07F);       \
-    __builtin_amdgcn_sched_barrier(0);        \
-  } while (0)
   const bool g1 = wr == 1;  // wave-uniform (wave came through readfirstlane)
   // prologue = the steady-state issue order up to "end of phase B of K-tile -1"
   stage(sB[0], UB0, 0, 0);
@@ -942,8 +967,8 @@ __global__ __launch_bounds__(512) void gemm_tn_t4_kernel(const GemmArgs p) {
   stage(sB[0], UB0, 1, 1);
   stage(sB[1], UB1, 1, 1);
   wait_vm<6>();
-  T4_BAR();
-  if (g1) T4_BAR();
+  pp_bar();
+  if (g1) pp_bar();
   for (int t = 0; t < nk; ++t) {
     const int b = t & 1;
     const char* cur = smem + b * STAGE;
@@ -952,31 +977,29 @@ __global__ __launch_bounds__(512) void gemm_tn_t4_kernel(const GemmArgs p) {
     loadA(cur, 0);
     stage(sA[0], UA0, t + 1, b ^ 1);
     stage(sA[1], UA1, t + 1, b ^ 1);
-    T4_LGKM0();
+    pp_lgkm0();
     if (g1) wait_vm<8>();
-    T4_BAR();
+    pp_bar();
     __builtin_amdgcn_s_setprio(1);
     mm(0, 0);
     mm(0, 1);
     __builtin_amdgcn_s_setprio(0);
     if (!g1) wait_vm<8>();
-    T4_BAR();
+    pp_bar();
     loadA(cur, 1);  // phase B
     stage(sB[0], UB0, t + 2, b);
     stage(sB[1], UB1, t + 2, b);
-    T4_LGKM0();
+    pp_lgkm0();
     if (g1) wait_vm<6>();
-    T4_BAR();
+    pp_bar();
     __builtin_amdgcn_s_setprio(1);
     mm(1, 1);
     mm(1, 0);
     __builtin_amdgcn_s_setprio(0);
     if (!g1) wait_vm<6>();
-    T4_BAR();
+    pp_bar();
   }
-  if (!g1) T4_BAR();
-#undef T4_BAR
-#undef T4_LGKM0
+  if (!g1) pp_bar();
   wait_vm<0>();  // never leave an LDS-DMA in flight past the end of the workgroup
   constexpr int OSZ = out_size<OUT>();
   const __amdgpu_buffer_rsrc_t crc =
@@ -1002,7 +1025,6 @@ __global__ __launch_bounds__(512) void gemm_tn_t4_kernel(const GemmArgs p) {
     }
   }
 }
-
 
 // ---------------------------------------------------------------- pt4: persistent t4
 // t4 streamed across a block's tiles (as pt8 does for t8). A tile's quadrants are stored right
@@ -1585,8 +1607,7 @@ __global__ __launch_bounds__(512) void gemm_tn_pt4_kernel(const GemmArgs p) {
 // Measured (research/lab, profiles/r01/s2/lab/): 65536x1024x1024 bf16 0.1116 ms vs t8 0.1163.
 template <class Mma, int OUT>
 __global__ __launch_bounds__(512) void gemm_tn_pt8_kernel(const GemmArgs p) {
-  constexpr int ROWB = 128, UNIT = 128 * ROWB, STAGE = 4 * UNIT;
-  constexpr int UA0 = 0, UA1 = UNIT, UB0 = 2 * UNIT, UB1 = 3 * UNIT;
+  using namespace pp;
   constexpr int NS = 4 * Store8<OUT>::kStores;  // C store instructions per quadrant per wave
   constexpr int OSZ = out_size<OUT>();
   __shared__ __attribute__((aligned(1024))) char smem[2 * STAGE];
@@ -1639,10 +1660,7 @@ __global__ __launch_bounds__(512) void gemm_tn_pt8_kernel(const GemmArgs p) {
       set_src(c.ti);
       src_tile = c.ti;
     }
-    const char* const* src = which < 2 ? sA[which] : sB[which - 2];
-    char* dst = smem + buf * STAGE + unit_off + wave * 16 * ROWB;
-    glds16(src[0] + (int64_t)c.kt * ROWB, dst);
-    glds16(src[1] + (int64_t)c.kt * ROWB, dst + 8 * ROWB);
+    pp_stage(which < 2 ? sA[which] : sB[which - 2], c.kt, smem + buf * STAGE + unit_off, wave);
   };
 
   const int frow = lane & 15, fq = lane >> 4, sw = (frow >> 1) & 7;
@@ -1733,12 +1751,6 @@ __global__ __launch_bounds__(512) void gemm_tn_pt8_kernel(const GemmArgs p) {
     }
     __builtin_amdgcn_sched_barrier(0);
   };
-#define T8_BAR()                         \
-  do {                                   \
-    __builtin_amdgcn_sched_barrier(0);   \
-    __builtin_amdgcn_s_barrier();        \
-    __builtin_amdgcn_sched_barrier(0);   \
-  } while (0)
 
   Cur q0{0, 0}, q1{0, 0};
   adv(q1);
@@ -1751,9 +1763,9 @@ __global__ __launch_bounds__(512) void gemm_tn_pt8_kernel(const GemmArgs p) {
   Cur q2 = q1;
   adv(q2);
   wait_vm<4>();
-  T8_BAR();
+  pp_bar();
   const bool g1 = wr == 1;  // wave-uniform (wave came through readfirstlane)
-  if (g1) T8_BAR();
+  if (g1) pp_bar();
   // one K-tile of the stream; LAST = the tile's last K-tile (stores its quadrants)
   auto iter = [&](int h, auto last_tag) __attribute__((always_inline)) {
     constexpr bool LAST = decltype(last_tag)::value;
@@ -1762,31 +1774,31 @@ __global__ __launch_bounds__(512) void gemm_tn_pt8_kernel(const GemmArgs p) {
     loadA(cur, 0);  // p0
     loadB(cur, 0);
     stage(1, UA1, q1, nb);
-    T8_BAR();
+    pp_bar();
     comp(0, 0);
     if constexpr (LAST) store_q(0, 0);
-    T8_BAR();
+    pp_bar();
     loadB(cur, 1);  // p1
     stage(2, UB0, q1, nb);
-    T8_BAR();
+    pp_bar();
     comp(0, 1);
     if constexpr (LAST) store_q(0, 1);
-    T8_BAR();
+    pp_bar();
     loadA(cur, 1);  // p2
     stage(0, UA0, q2, b);
-    T8_BAR();
+    pp_bar();
     comp(1, 1);
     if constexpr (LAST) store_q(1, 1);
-    T8_BAR();
+    pp_bar();
     loadB(cur, 0);  // p3
     stage(3, UB1, q2, b);
     // younger than UB0(h+1): UA0/UB1(h+2) and, in a tile's last K-tile, the Q01 + Q11 stores
     if (g1) wait_vm<LAST ? 4 + 2 * NS : 4>();
-    T8_BAR();
+    pp_bar();
     comp(1, 0);
     if constexpr (LAST) store_q(1, 0);
     if (!g1) wait_vm<LAST ? 4 + 3 * NS : 4>();  // ... and Q10
-    T8_BAR();
+    pp_bar();
     q1 = q2;
     adv(q2);
   };
@@ -1796,119 +1808,8 @@ __global__ __launch_bounds__(512) void gemm_tn_pt8_kernel(const GemmArgs p) {
     iter(h, std::integral_constant<bool, true>{});
     ++h;
   }
-  if (!g1) T8_BAR();
-#undef T8_BAR
+  if (!g1) pp_bar();
   wait_vm<0>();  // never leave an LDS-DMA in flight past the end of the workgroup
-}
-
-// ---------------------------------------------------------------- MX-fp8 (block-scaled) kernel
-// One v_mfma_scale_f32_16x16x128_f8f6f4 per 128-byte K-row (unit E8M0 scales = 127): 2x the bf16
-// MFMA rate (MI355X_MICROARCH.md "Matrix cores"). Same staging as above.
-template <int OUT, int BM, int BN, int WM, int WN>
-__global__ __launch_bounds__(WM* WN * 64) void gemm_tn_mxfp8_kernel(const GemmArgs p) {
-  constexpr int NW = WM * WN, ROWB = 128;
-  constexpr int A_BYTES = BM * ROWB, B_BYTES = BN * ROWB, STAGE = A_BYTES + B_BYTES;
-  constexpr int TM = BM / WM, TN = BN / WN, MR = TM / 16, NR = TN / 16;
-  constexpr int LA = BM / 8 / NW, LB = BN / 8 / NW;
-  __shared__ __attribute__((aligned(1024))) char smem[2 * STAGE];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tiles_n = (p.N + BN - 1) / BN, tiles_m = (p.M + BM - 1) / BM;
-  const int nwg = tiles_m * tiles_n;
-  const int wg = tile_index(p, nwg);
-  const int tm = wg / tiles_n, tn = wg % tiles_n;
-  const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
-  const char* aptr[LA];
-  const char* bptr[LB];
-#pragma unroll
-  for (int i = 0; i < LA; ++i) {
-    const int row = (wave * LA + i) * 8 + (lane >> 3);
-    int64_t gr = m0 + row;
-    gr = gr < p.M ? gr : p.M - 1;
-    const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-    aptr[i] = (const char*)p.a + map_row(gr, p.a_grp, p.a_gstride) * p.lda + chunk * 16;
-  }
-#pragma unroll
-  for (int i = 0; i < LB; ++i) {
-    const int row = (wave * LB + i) * 8 + (lane >> 3);
-    int64_t gr = n0 + row;
-    gr = gr < p.N ? gr : p.N - 1;
-    const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-    bptr[i] = (const char*)p.b + gr * p.ldb + chunk * 16;
-  }
-  wait_tile(p, m0, BM);
-  auto stage = [&](int buf, int kt) __attribute__((always_inline)) {
-    char* base = smem + buf * STAGE;
-    const int64_t koff = (int64_t)kt * ROWB;
-#pragma unroll
-    for (int i = 0; i < LA; ++i) glds16(aptr[i] + koff, base + (wave * LA + i) * 1024);
-#pragma unroll
-    for (int i = 0; i < LB; ++i) glds16(bptr[i] + koff, base + A_BYTES + (wave * LB + i) * 1024);
-  };
-  const int wm = wave / WN, wn = wave % WN;
-  const int swz = (lane & 15) >> 1, frow = lane & 15, fq = lane >> 4;
-  f32x4 acc[MR][NR];
-#pragma unroll
-  for (int i = 0; i < MR; ++i)
-#pragma unroll
-    for (int j = 0; j < NR; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto compute = [&](int buf) __attribute__((always_inline)) {
-    const char* As = smem + buf * STAGE;
-    const char* Bs = As + A_BYTES;
-    const int c0 = ((fq) ^ swz) * 16, c1 = ((4 + fq) ^ swz) * 16;
-    i32x8 af[MR], bfr[NR];
-#pragma unroll
-    for (int i = 0; i < MR; ++i) {
-      const char* r = As + (wm * TM + i * 16 + frow) * ROWB;
-      const i32x4 lo = *(const i32x4*)(r + c0), hi = *(const i32x4*)(r + c1);
-      af[i] = i32x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    }
-#pragma unroll
-    for (int j = 0; j < NR; ++j) {
-      const char* r = Bs + (wn * TN + j * 16 + frow) * ROWB;
-      const i32x4 lo = *(const i32x4*)(r + c0), hi = *(const i32x4*)(r + c1);
-      bfr[j] = i32x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    }
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < MR; ++i)
-#pragma unroll
-      for (int j = 0; j < NR; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(bfr[j], af[i], acc[i][j], 0,
-                                                                       0, 0, 127, 0, 127);
-    __builtin_amdgcn_s_setprio(0);
-  };
-  const int nk = p.K / ROWB;
-  stage(0, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  int cur = 0;
-  for (int kt = 0; kt < nk - 1; ++kt) {
-    stage(cur ^ 1, kt + 1);
-    compute(cur);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    cur ^= 1;
-  }
-  compute(cur);
-  constexpr int OSZ = out_size<OUT>();
-#pragma unroll
-  for (int i = 0; i < MR; ++i) {
-    const int64_t row = m0 + wm * TM + i * 16 + frow;
-    if (row >= p.M) continue;
-    char* crow = c_row<OSZ>(p, row);
-#pragma unroll
-    for (int j = 0; j < NR; ++j) {
-      const int64_t col = n0 + wn * TN + j * 16 + fq * 4;
-      if (col + 3 < p.N) {
-        Store4<OUT>::st(crow + col * OSZ, act4(acc[i][j], p.act));
-      } else {
-        const f32x4 a4 = act4(acc[i][j], p.act);
-        const float v[4] = {a4.x, a4.y, a4.z, a4.w};
-        for (int r = 0; r < 4; ++r)
-          if (col + r < p.N) Store4<OUT>::st1(crow + (col + r) * OSZ, v[r]);
-      }
-    }
-  }
 }
 
 // ---------------------------------------------------------------- generic fallback kernel
@@ -1972,19 +1873,31 @@ __global__ __launch_bounds__(256) void gemm_generic_kernel(const GemmArgs p) {
 }
 
 // ---------------------------------------------------------------- dispatch
-template <class Mma, int OUT, int BM, int BN, int WM, int WN, bool ILV = false>
-hipError_t launch_tiled(const GemmArgs& p, hipStream_t s) {
-  const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-  hipLaunchKernelGGL((gemm_tn_kernel<Mma, OUT, BM, BN, WM, WN, ILV>), dim3(tiles),
-                     dim3(WM * WN * 64), 0, s, p);
-  return hipGetLastError();
+// f(std::integral_constant<int, v>{}) for the run-time v in [0, N): a run-time choice among
+// compile-time configurations with ONE call site in f.
+template <int N, class F>
+hipError_t dispatch_int(int v, F&& f) {
+  if constexpr (N == 0) {
+    return hipErrorInvalidValue;
+  } else {
+    if (v == N - 1) return f(std::integral_constant<int, N - 1>{});
+    return dispatch_int<N - 1>(v, f);
+  }
 }
-template <int OUT, int BM, int BN, int WM, int WN>
-hipError_t launch_mx(const GemmArgs& p, hipStream_t s) {
-  const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-  hipLaunchKernelGGL((gemm_tn_mxfp8_kernel<OUT, BM, BN, WM, WN>), dim3(tiles),
-                     dim3(WM * WN * 64), 0, s, p);
-  return hipGetLastError();
+
+// The tiled kernel of a tile code (gemm.h kTileCfgs: for the ping-pong codes the interleaved
+// 256x256 one, which takes what they do not); the MX kernels are never interleaved.
+// hipErrorInvalidValue for a code without a kernel (5, 8, 9, 13-15: retired kernel families).
+template <class Mma, int OUT>
+hipError_t launch_tiled(const GemmArgs& p, int tile, hipStream_t s) {
+  return dispatch_int<kNumTileCfgs>(tile_slot(tile), [&](auto slot) {
+    constexpr TileCfg c = kTileCfgs[decltype(slot)::value];
+    constexpr bool ILV = c.ilv && !is_pair<Mma>::value;
+    const int tiles = ((p.M + c.rows - 1) / c.rows) * ((p.N + c.cols - 1) / c.cols);
+    hipLaunchKernelGGL((gemm_tn_kernel<Mma, OUT, c.rows, c.cols, c.wm, c.wn, ILV>), dim3(tiles),
+                       dim3(c.wm * c.wn * 64), 0, s, p);
+    return hipGetLastError();
+  });
 }
 
 int num_cus() {
@@ -2070,45 +1983,37 @@ hipError_t launch_pt4(const GemmArgs& p, hipStream_t s) {
   const bool wt = c_fits_wt(p, out_size<OUT>()) && p.c_grp % 256 == 0;
   // A through grouped rows / a row-block table: the APAN instantiations (no C row table with them)
   const bool apan = p.a_table != nullptr || p.a_grp != p.M;
+  // One launch site for the ten kernels: form = GATED * 6 + APAN * 3 + CMODE, 12 = the K-split
+  // (ungated, plain rows, CMODE 2).
+  const bool gated = p.flags != nullptr;
+  int form;
   if (p.ksplit > 1) {  // (gemm_launch routes only eligible K-splits here: plain rows, ungated)
-    if (p.flags != nullptr || apan || p.c_table != nullptr || p.c_grp != p.M || !wt)
+    if (gated || apan || p.c_table != nullptr || p.c_grp != p.M || !wt)
       return hipErrorNotSupported;
     if ((int64_t)p.ksplit * p.M * p.ldc * out_size<OUT>() >= 0x7FFFFFF0LL)
       return hipErrorNotSupported;
-    hipLaunchKernelGGL((gemm_tn_pt4_kernel<Mma, OUT, false, 2, false, true>), dim3(grid),
-                       dim3(512), 0, s, q);
-    return hipGetLastError();
+    form = 12;
+  } else {
+    if (apan && p.c_table != nullptr) return hipErrorNotSupported;
+    // tile_order 3 promises that the first producer's rows are never gated; only the table /
+    // grouped A (APAN) gated instantiation implements that skip (OWN), so anything else is refused
+    // rather than left to spin on a flag nobody raises
+    if (gated && p.tile_order == 3 && !apan) return hipErrorNotSupported;
+    form = gated * 6 + apan * 3 + (wt ? 2 : (!gated && !apan && p.c_table != nullptr ? 1 : 0));
   }
-  if (apan && p.c_table != nullptr) return hipErrorNotSupported;
-  // tile_order 3 promises that the first producer's rows are never gated; only the table / grouped
-  // A (APAN) gated instantiation implements that skip (OWN), so anything else is refused rather
-  // than left to spin on a flag nobody raises
-  if (p.flags != nullptr && p.tile_order == 3 && !apan) return hipErrorNotSupported;
-  if (apan && p.flags != nullptr && wt)
-    hipLaunchKernelGGL((gemm_tn_pt4_kernel<Mma, OUT, true, 2, true>), dim3(grid + q.ag_ctas),
-                       dim3(512), 0, s, q);
-  else if (apan && p.flags != nullptr)
-    hipLaunchKernelGGL((gemm_tn_pt4_kernel<Mma, OUT, true, 0, true>), dim3(grid + q.ag_ctas),
-                       dim3(512), 0, s, q);
-  else if (apan && wt)
-    hipLaunchKernelGGL((gemm_tn_pt4_kernel<Mma, OUT, false, 2, true>), dim3(grid), dim3(512), 0, s,
-                       p);
-  else if (apan)
-    hipLaunchKernelGGL((gemm_tn_pt4_kernel<Mma, OUT, false, 0, true>), dim3(grid), dim3(512), 0, s,
-                       p);
-  else if (p.flags != nullptr && wt)
-    hipLaunchKernelGGL((gemm_tn_pt4_kernel<Mma, OUT, true, 2>), dim3(grid + q.ag_ctas), dim3(512),
-                       0, s, q);
-  else if (p.flags != nullptr)
-    hipLaunchKernelGGL((gemm_tn_pt4_kernel<Mma, OUT, true>), dim3(grid + q.ag_ctas), dim3(512), 0,
-                       s, q);
-  else if (p.c_table != nullptr)
-    hipLaunchKernelGGL((gemm_tn_pt4_kernel<Mma, OUT, false, 1>), dim3(grid), dim3(512), 0, s, p);
-  else if (wt)
-    hipLaunchKernelGGL((gemm_tn_pt4_kernel<Mma, OUT, false, 2>), dim3(grid), dim3(512), 0, s, p);
-  else
-    hipLaunchKernelGGL((gemm_tn_pt4_kernel<Mma, OUT, false>), dim3(grid), dim3(512), 0, s, p);
-  return hipGetLastError();
+  return dispatch_int<13>(form, [&](auto fc) {
+    constexpr int F = decltype(fc)::value;
+    constexpr bool KS = F == 12, G = !KS && F / 6 == 1, A = !KS && F / 3 % 2 == 1;
+    constexpr int C = KS ? 2 : F % 3;
+    if constexpr (C == 1 && (G || A)) {
+      return hipErrorNotSupported;  // (never chosen above: a C row table goes with plain A rows)
+    } else {
+      // the gated forms carry the copy workgroups (q.ag_ctas, may be 0) in front of the GEMM's
+      hipLaunchKernelGGL((gemm_tn_pt4_kernel<Mma, OUT, G, C, A, KS>),
+                         dim3(G ? grid + q.ag_ctas : grid), dim3(512), 0, s, G || KS ? q : p);
+      return hipGetLastError();
+    }
+  });
 }
 
 template <class Mma, int OUT>
@@ -2126,34 +2031,17 @@ hipError_t launch_pt8(const GemmArgs& p, hipStream_t s) {
 
 template <class Mma, int OUT>
 hipError_t launch_cfg(const GemmArgs& p, int tile, hipStream_t s) {
-  switch (tile) {
-    case TILE_PT8:  // persistent: no arrival flags (a block's tiles are fixed up front)
-      if (t8_ok(p) && p.flags == nullptr) return launch_pt8<Mma, OUT>(p, s);
-      if (t8_ok(p)) return launch_t8<Mma, OUT>(p, s);
-      return launch_tiled<Mma, OUT, 256, 256, 2, 4, true>(p, s);
-    case TILE_PT4:
-      if (pt4_ok(p, Mma::kElem) && !(p.c_table && (p.a_table || p.a_grp != p.M)))
-        return launch_pt4<Mma, OUT>(p, s);
-      if (p.ksplit > 1) return hipErrorNotSupported;  // only pt4 runs (slice, tile) pairs
-      if (t8_ok(p)) return launch_t4<Mma, OUT>(p, s);
-      return launch_tiled<Mma, OUT, 256, 256, 2, 4, true>(p, s);
-    case TILE_T4:
-      if (t8_ok(p)) return launch_t4<Mma, OUT>(p, s);
-      return launch_tiled<Mma, OUT, 256, 256, 2, 4, true>(p, s);
-    case TILE_T8:
-      if (t8_ok(p)) return launch_t8<Mma, OUT>(p, s);
-      return launch_tiled<Mma, OUT, 256, 256, 2, 4, true>(p, s);
-    case TILE_256x256: return launch_tiled<Mma, OUT, 256, 256, 2, 4>(p, s);
-    case TILE_256x128: return launch_tiled<Mma, OUT, 256, 128, 4, 2>(p, s);
-    case TILE_128x256: return launch_tiled<Mma, OUT, 128, 256, 2, 4>(p, s);
-    case TILE_128x128: return launch_tiled<Mma, OUT, 128, 128, 2, 2>(p, s);
-    case TILE_256x256_W4: return launch_tiled<Mma, OUT, 256, 256, 2, 2>(p, s);
-    case TILE_256x128_W4: return launch_tiled<Mma, OUT, 256, 128, 2, 2>(p, s);
-    case TILE_I256: return launch_tiled<Mma, OUT, 256, 256, 2, 4, true>(p, s);
-    case TILE_I128: return launch_tiled<Mma, OUT, 128, 128, 2, 2, true>(p, s);
-    case TILE_I256W4: return launch_tiled<Mma, OUT, 256, 256, 2, 2, true>(p, s);
-    default: return hipErrorInvalidValue;  // (5, 8, 9, 13-15: retired kernel families)
+  // whole 256x256 tiles: the ping-pong kernels. pt8 is persistent: no arrival flags (a block's
+  // tiles are fixed up front)
+  if (tile == TILE_PT8 && t8_ok(p) && p.flags == nullptr) return launch_pt8<Mma, OUT>(p, s);
+  if (tile == TILE_PT4) {
+    if (pt4_ok(p, Mma::kElem) && !(p.c_table && (p.a_table || p.a_grp != p.M)))
+      return launch_pt4<Mma, OUT>(p, s);
+    if (p.ksplit > 1) return hipErrorNotSupported;  // only pt4 runs (slice, tile) pairs
   }
+  if ((tile == TILE_T4 || tile == TILE_PT4) && t8_ok(p)) return launch_t4<Mma, OUT>(p, s);
+  if ((tile == TILE_T8 || tile == TILE_PT8) && t8_ok(p)) return launch_t8<Mma, OUT>(p, s);
+  return launch_tiled<Mma, OUT>(p, tile, s);
 }
 template <int OUT>
 hipError_t launch_mx_cfg(const GemmArgs& p, int tile, hipStream_t s) {
@@ -2168,20 +2056,7 @@ hipError_t launch_mx_cfg(const GemmArgs& p, int tile, hipStream_t s) {
       return launch_pt8<MmaMX, OUT>(p, s);
     return launch_t8<MmaMX, OUT>(p, s);
   }
-  switch (tile) {
-    case TILE_256x256: return launch_mx<OUT, 256, 256, 2, 4>(p, s);
-    case TILE_256x128: return launch_mx<OUT, 256, 128, 4, 2>(p, s);
-    case TILE_128x256: return launch_mx<OUT, 128, 256, 2, 4>(p, s);
-    case TILE_128x128: return launch_mx<OUT, 128, 128, 2, 2>(p, s);
-    case TILE_256x256_W4: return launch_mx<OUT, 256, 256, 2, 2>(p, s);
-    case TILE_I256: return launch_mx<OUT, 256, 256, 2, 4>(p, s);
-    case TILE_I128: return launch_mx<OUT, 128, 128, 2, 2>(p, s);
-    case TILE_I256W4: return launch_mx<OUT, 256, 256, 2, 2>(p, s);
-    case TILE_T8: case TILE_PT8: case TILE_T4: case TILE_PT4:
-      return launch_mx<OUT, 256, 256, 2, 4>(p, s);
-    case TILE_256x128_W4: return launch_mx<OUT, 256, 128, 2, 2>(p, s);
-    default: return hipErrorInvalidValue;  // (5, 8, 9, 13-15: retired kernel families)
-  }
+  return launch_tiled<MmaMX, OUT>(p, tile, s);
 }
 
 template <int DIN, int DOUT>

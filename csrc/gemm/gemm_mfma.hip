@@ -36,13 +36,8 @@
 
 namespace ddlb {
 
-int tile_rows(int tile) {
-  return (tile == TILE_128x128 || tile == TILE_128x256 || tile == TILE_I128) ? 128 : 256;
-}
-int tile_cols(int tile) {
-  return (tile == TILE_256x128 || tile == TILE_128x128 || tile == TILE_256x128_W4 ||
-          tile == TILE_I128) ? 128 : 256;
-}
+int tile_rows(int tile) { return tile_rows_of(tile); }
+int tile_cols(int tile) { return tile_cols_of(tile); }
 
 bool gemm_fast_path_ok(const GemmArgs& p, int din, int dout) {
   const int esz = dtype_size(din);
@@ -84,12 +79,8 @@ hipError_t gemm_launch(const GemmArgs& p_in, int din, int dout, int tile, int mo
   GemmArgs p = p_in;
   if (p.a_grp <= 0) { p.a_grp = p.M > 0 ? p.M : 1; p.a_gstride = p.a_grp; }
   if (p.c_grp <= 0) { p.c_grp = p.M > 0 ? p.M : 1; p.c_gstride = p.c_grp; }
-  switch (tile) {  // known codes only (the retired families' codes are refused, not rerouted)
-    case TILE_AUTO: case TILE_256x256: case TILE_256x128: case TILE_128x256: case TILE_128x128:
-    case TILE_256x256_W4: case TILE_256x128_W4: case TILE_I256: case TILE_I128: case TILE_I256W4:
-    case TILE_T8: case TILE_PT8: case TILE_T4: case TILE_PT4: break;
-    default: return hipErrorInvalidValue;
-  }
+  // known codes only (the retired families' codes are refused, not rerouted)
+  if (tile != TILE_AUTO && tile_slot(tile) < 0) return hipErrorInvalidValue;
   if (p.M == 0 || p.N == 0) return hipSuccess;
   if (p.ksplit > 1) {
     // K-split: slice j of K columns -> partial j at c + j * M * ldc (the caller sums them). pt4

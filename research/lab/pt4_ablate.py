@@ -531,12 +531,14 @@ PINNED = {
 
 # The pinned revisions' gemm_kernels.h is rebuilt without git history (a shallow or exported
 # checkout has none): research/lab/pinned/ holds a chain of diffs that walks back from the
-# product header (identical to fc1ce0f's) one distinct revision at a time; revisions whose header
-# is byte-identical share a step. The other two headers (gemm.h, tile_map.h) did not change since
-# the oldest pinned revision and come from the working tree. Each rebuilt header is checked
-# against the sha256 of the text that was measured, so an edit of the product header that the
-# chain no longer fits fails loudly (then: re-base pinned/1_*.diff on the new product header).
-CHAIN = ["fc1ce0f", "cb084d4", "e2c6c5f", "34f0106", "38ab6ea", "2c4e4ca"]  # newest first
+# product header (CHAIN[0]: the shared ping-pong core, pt4's text as at fc1ce0f) one distinct
+# revision at a time; revisions whose header is byte-identical share a step. The other two
+# headers (gemm.h, tile_map.h) come from the working tree: they only gained declarations since
+# the oldest pinned revision. Each rebuilt header is checked against the sha256 of the text that
+# was measured, so an edit of the product header that the chain no longer fits fails loudly
+# (then: re-base pinned/1_*.diff on the new product header, or add a step in front as here).
+CHAIN = ["pp-core", "fc1ce0f", "cb084d4", "e2c6c5f", "34f0106", "38ab6ea",
+         "2c4e4ca"]  # newest first; CHAIN[0] labels the product header, the rest are revisions
 SAME_AS = {"b8b30bb": "34f0106", "8c58daa": "34f0106", "d2e1ff0": "fc1ce0f"}
 SHA256 = {"fc1ce0f": "dcc3f42196ae3f21", "cb084d4": "069e0c68d325214b",
           "e2c6c5f": "dad98a5e8633ae95", "34f0106": "420c39d05549ebc9",

@@ -113,6 +113,50 @@ def test_fp8_integer_exact(gen, tile):
         assert torch.equal(out, ref), mode
 
 
+@pytest.fixture(scope="module")
+def mx_ragged():
+    """Integer-valued e4m3 operands of a ragged GEMM and their (exact) fp32 product (a generator
+    of its own: the other tests' draws from ``gen`` stay what they were)."""
+    M, N, K = 300, 202, 256
+    gen = torch.Generator(device=DEV)
+    gen.manual_seed(4321)
+    a = torch.randint(-3, 4, (M, K), device=DEV, generator=gen).float().to(torch.float8_e4m3fn)
+    w = torch.randint(-3, 4, (N, K), device=DEV, generator=gen).float().to(torch.float8_e4m3fn)
+    return a, w, _ref(a, w)
+
+
+@pytest.mark.parametrize("tile", ["128x128", "256x128", "128x256"])
+def test_mx_tiled_ragged_exact(mx_ragged, tile):
+    """The tiled kernel with block-scaled MFMAs off the whole-tile shapes: M = 300 reaches the
+    clamped row loads, N = 202 the scalar column tail (202 % 4 != 0; 202 * 4 bytes keeps the f32
+    rows 8-byte aligned, so the fast path takes it)."""
+    from ddlb_amd.ops.gemm import gemm
+
+    a, w, ref = mx_ragged
+    out = gemm(a, w, out_dtype=torch.float32, mode="mx", tile=tile)
+    torch.cuda.synchronize()
+    assert torch.equal(out, ref)
+
+
+def test_mx_tiled_ragged_grouped_rows(mx_ragged):
+    """The same product with A read from and C written to groups of 100 rows 128 apart."""
+    from ddlb_amd.ops.gemm import gemm
+
+    a, w, ref = mx_ragged
+    M, N, grp, gs = a.shape[0], w.shape[0], 100, 128
+    phys = torch.cat([torch.arange(g * gs, g * gs + grp, device=DEV) for g in range(M // grp)])
+    A = torch.zeros((M // grp * gs, a.shape[1]), dtype=torch.float32, device=DEV)
+    A[phys] = a.float()
+    C = torch.full((M // grp * gs, N), -7.0, dtype=torch.float32, device=DEV)
+    gemm(A.to(torch.float8_e4m3fn), w, C, M=M, a_grp=grp, a_gstride=gs, c_grp=grp, c_gstride=gs,
+         mode="mx", tile="128x128")
+    torch.cuda.synchronize()
+    assert torch.equal(C[phys], ref)
+    untouched = torch.ones(C.shape[0], dtype=torch.bool, device=DEV)
+    untouched[phys] = False
+    assert torch.all(C[untouched] == -7.0)
+
+
 def test_grouped_rows(gen):
     """Pipeline addressing: A rows from strided blocks, C rows to strided blocks."""
     from ddlb_amd.ops.gemm import gemm
