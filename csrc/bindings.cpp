@@ -135,18 +135,41 @@ PYBIND11_MODULE(_C, m) {
   m.def("gemm",
         [](uintptr_t a, uintptr_t b, uintptr_t c, int64_t lda, int64_t ldb, int64_t ldc, int M,
            int N, int K, int din, int dout, int tile, int mode, int64_t a_grp, int64_t a_gstride,
-           int64_t c_grp, int64_t c_gstride, uintptr_t stream, int act, int ksplit) {
+           int64_t c_grp, int64_t c_gstride, uintptr_t stream, int act, int ksplit,
+           uintptr_t a_scale, uintptr_t b_scale, int64_t a_scale_ld, int64_t b_scale_ld) {
           GemmArgs g = make_args(a, b, c, lda, ldb, ldc, M, N, K, a_grp, a_gstride, c_grp,
                                  c_gstride);
           g.act = act;
           g.ksplit = ksplit > 1 ? ksplit : 1;
+          g.a_scale = (const uint8_t*)a_scale;
+          g.b_scale = (const uint8_t*)b_scale;
+          g.a_scale_ld = a_scale_ld;
+          g.b_scale_ld = b_scale_ld;
           check(gemm_launch(g, din, dout, tile, mode, (hipStream_t)stream), "gemm_launch");
         },
         py::arg("a"), py::arg("b"), py::arg("c"), py::arg("lda"), py::arg("ldb"), py::arg("ldc"),
         py::arg("M"), py::arg("N"), py::arg("K"), py::arg("din"), py::arg("dout"),
         py::arg("tile") = 0, py::arg("mode") = 0, py::arg("a_grp") = 0, py::arg("a_gstride") = 0,
         py::arg("c_grp") = 0, py::arg("c_gstride") = 0, py::arg("stream") = 0,
-        py::arg("act") = 0, py::arg("ksplit") = 1);
+        py::arg("act") = 0, py::arg("ksplit") = 1, py::arg("a_scale") = 0,
+        py::arg("b_scale") = 0, py::arg("a_scale_ld") = 0, py::arg("b_scale_ld") = 0);
+  m.def("mx_quantize",  // x[R, K] f32 / f16 / bf16 -> q[R, K] e4m3 + s[R, K / 32] E8M0 bytes
+        [](uintptr_t x, uintptr_t q, uintptr_t sc, int64_t ldx, int64_t ldq, int64_t lds, int R,
+           int K, int din, uintptr_t stream) {
+          MxQuantArgs a;
+          a.x = (const void*)x; a.q = (void*)q; a.s = (uint8_t*)sc;
+          a.ldx = ldx; a.ldq = ldq; a.lds = lds;
+          a.R = R; a.K = K;
+          check(mx_quantize_launch(a, din, (hipStream_t)stream), "mx_quantize");
+        },
+        py::arg("x"), py::arg("q"), py::arg("s"), py::arg("ldx"), py::arg("ldq"),
+        py::arg("lds"), py::arg("R"), py::arg("K"), py::arg("din"), py::arg("stream") = 0);
+  m.attr("MXS_TILES") = [] {  // tile codes the block-scaled GEMM is built for
+    std::vector<int> v;
+    for (int i = 0; i < kNumTileCfgs; ++i)
+      if (mxs_offers(kTileCfgs[i].code)) v.push_back(kTileCfgs[i].code);
+    return v;
+  }();
   m.def("gemm_fast_path_ok",
         [](uintptr_t a, uintptr_t b, uintptr_t c, int64_t lda, int64_t ldb, int64_t ldc, int M,
            int N, int K, int din, int dout) {

@@ -56,6 +56,29 @@ constexpr int tile_cols_of(int tile) {
   return i < 0 ? 256 : kTileCfgs[i].cols;
 }
 
+// Tile codes the scaled (per-block E8M0 scales) flavour of the tiled kernel is built for. Both
+// 256x256 forms are left out: on top of their accumulator and fragment registers the scale
+// offsets, words and bytes (3 per fragment) do not fit, and the compiler spills to scratch
+// (TILE_256x256, 2x4 waves: 292 bytes per lane; TILE_256x256_W4: 44; docs/ARCHITECTURE.md).
+constexpr bool mxs_offers(int tile) {
+  return tile == TILE_256x128 || tile == TILE_128x256 || tile == TILE_128x128 ||
+         tile == TILE_256x128_W4;
+}
+// The scaled kernel for what choose_tile answers (`auto` only; an explicit code that is not
+// offered, the ping-pong codes among them, is refused): an offered code is itself; any other
+// live code maps to the offered code of its rows x cols, a 256x256 one to 256x128. -1: not a
+// live code.
+constexpr int mxs_tile_for(int tile) {
+  if (mxs_offers(tile)) return tile;
+  const int i = tile_slot(tile);
+  if (i < 0) return -1;
+  for (int j = 0; j < kNumTileCfgs; ++j)
+    if (mxs_offers(kTileCfgs[j].code) && kTileCfgs[j].rows == kTileCfgs[i].rows &&
+        kTileCfgs[j].cols == kTileCfgs[i].cols)
+      return kTileCfgs[j].code;
+  return TILE_256x128;
+}
+
 constexpr bool tile_cfgs_distinct() {
   for (int i = 0; i < kNumTileCfgs; ++i)
     for (int j = i + 1; j < kNumTileCfgs; ++j)
@@ -131,6 +154,13 @@ struct GemmArgs {
   // c + s * M * ldc elements (the caller sums the partials). pt4 runs every (slice, tile) in one
   // launch; other kernels run the slices one after another.
   int ksplit = 1;
+  // MX block scales (optional, fp8 inputs; both or neither): one E8M0 byte (value 2^(s - 127))
+  // per 32 consecutive K elements of a row, row-major [rows, K / 32] with a row stride of
+  // a_scale_ld / b_scale_ld BYTES (a multiple of 4, base 4-byte aligned), so the four scales of a
+  // row's 128-byte K-tile are one aligned 32-bit word. Null: unit scales, the kernels above.
+  const uint8_t* a_scale = nullptr;
+  const uint8_t* b_scale = nullptr;
+  int64_t a_scale_ld = 0, b_scale_ld = 0;
 };
 enum Act : int { ACT_NONE = 0, ACT_GELU = 1, ACT_RELU = 2, ACT_SILU = 3 };
 // In-kernel all-gather variants (GemmArgs::ag_mode bits; 0 = write-through publication, 8 loads
@@ -144,6 +174,20 @@ enum AgMode : int {
   AG_WAIT_ACKS = 16,       // copy workgroup 0 waits for every peer's ACK before the launch ends
                            // (ag_tab then has np more entries: my local ACK word per producer)
 };
+
+// MX quantiser (csrc/gemm/mx_quant.hip): x[R, K] (f32 / f16 / bf16 rows, ldx ELEMENTS apart) ->
+// q[R, K] e4m3 (rows ldq bytes apart) and s[R, K / 32] E8M0 bytes (rows lds bytes apart), one
+// scale per 32 consecutive K elements: the smallest power of two 2^e with amax / 2^e <= 448
+// (e clamped to [-127, 127], an all-zero block gets e = 0), s = e + 127, q = rne(x / 2^e).
+// K % 128 == 0; x rows 16-byte and q rows 8-byte aligned (checked by the caller, and here).
+struct MxQuantArgs {
+  const void* x = nullptr;
+  void* q = nullptr;
+  uint8_t* s = nullptr;
+  int64_t ldx = 0, ldq = 0, lds = 0;
+  int R = 0, K = 0;
+};
+hipError_t mx_quantize_launch(const MxQuantArgs& a, int din, hipStream_t s);
 
 hipError_t gemm_launch(const GemmArgs& p, int din, int dout, int tile, int mode, hipStream_t s);
 bool gemm_fast_path_ok(const GemmArgs& p, int din, int dout);

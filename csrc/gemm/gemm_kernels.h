@@ -111,9 +111,23 @@ struct MmaMX {
     acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(b, a, acc, 0, 0, 0, 127, 0, 127);
   }
 };
+// MX-fp8 with real block scales (kScaled): lane (lane & 15, lane >> 4) passes the E8M0 byte of
+// row lane & 15, K block lane >> 4 of the 128-byte K-row, for both operands (the instruction takes
+// block kb's scale from lane group kb, whichever lanes hold its data). Tiled kernel only.
+struct MmaMXS {
+  static constexpr int kElem = 1, kMfma = 1;
+  static constexpr bool kPair = true, kScaled = true;
+  static __device__ __forceinline__ void step8s(f32x4& acc, const i32x8& b, const i32x8& a,
+                                                int sb, int sa) {
+    acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(b, a, acc, 0, 0, 0, sb, 0, sa);
+  }
+};
 template <class Mma, class = void> struct is_pair : std::false_type {};
 template <class Mma> struct is_pair<Mma, std::void_t<decltype(Mma::kPair)>>
     : std::integral_constant<bool, Mma::kPair> {};
+template <class Mma, class = void> struct is_scaled : std::false_type {};
+template <class Mma> struct is_scaled<Mma, std::void_t<decltype(Mma::kScaled)>>
+    : std::integral_constant<bool, Mma::kScaled> {};
 
 // Compile-time emission of the {PER x MFMA, 1 x VMEM, n_g x DS_READ} interleave pattern
 // (sched_group_barrier arguments must be literal constants).
@@ -409,10 +423,62 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_tn_kernel(const GemmArgs p) 
 #pragma unroll
     for (int j = 0; j < NR; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+  // Block scales (MmaMXS): lane (frow, fq) supplies the scale of K block 4 kt + fq of its
+  // fragment rows. The row's four bytes of a K-tile are one 32-bit word, loaded from global
+  // memory (no LDS traffic) beside the DMA of the K-tile they belong to and first touched after
+  // the vmcnt(0) that ends the iteration: an ordinary load's result used while an LDS-DMA is in
+  // flight would make the compiler drain the DMA there. Rows are clamped as the data rows are.
+  constexpr bool SC = is_scaled<Mma>::value;
+  constexpr int NSA = SC ? MR : 1, NSB = SC ? NR : 1;
+  unsigned sa_off[NSA], sb_off[NSB];  // byte offset of each fragment's scale row
+  unsigned sa_w[NSA], sb_w[NSB];      // scale words in flight (the K-tile being staged)
+  int sa[NSA], sb[NSB];               // this K-tile's scale byte
+  if constexpr (SC) {
+#pragma unroll
+    for (int i = 0; i < MR; ++i) {
+      int64_t gr = m0 + wm * TM + i * 16 + frow;
+      gr = gr < p.M ? gr : p.M - 1;
+      sa_off[i] = (unsigned)(gr * p.a_scale_ld);
+    }
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+      int64_t gr = n0 + wn * TN + j * 16 + frow;
+      gr = gr < p.N ? gr : p.N - 1;
+      sb_off[j] = (unsigned)(gr * p.b_scale_ld);
+    }
+  }
+  auto load_scales = [&](int kt) __attribute__((always_inline)) {
+    if constexpr (SC) {
+      const GLB_AS char* ga = (const GLB_AS char*)p.a_scale + kt * 4;
+      const GLB_AS char* gb = (const GLB_AS char*)p.b_scale + kt * 4;
+#pragma unroll
+      for (int i = 0; i < MR; ++i) sa_w[i] = *(const GLB_AS unsigned*)(ga + sa_off[i]);
+#pragma unroll
+      for (int j = 0; j < NR; ++j) sb_w[j] = *(const GLB_AS unsigned*)(gb + sb_off[j]);
+    }
+  };
+  auto take_scales = [&]() __attribute__((always_inline)) {
+    if constexpr (SC) {
+      // (the fences keep these uses between the barrier and the next stage's DMA)
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = 0; i < MR; ++i) sa[i] = (int)__builtin_amdgcn_ubfe(sa_w[i], fq * 8, 8);
+#pragma unroll
+      for (int j = 0; j < NR; ++j) sb[j] = (int)__builtin_amdgcn_ubfe(sb_w[j], fq * 8, 8);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+
   auto compute = [&](int buf) __attribute__((always_inline)) {
     const char* As = smem + buf * STAGE;
     const char* Bs = As + A_BYTES;
     if constexpr (is_pair<Mma>::value) {  // MX: one scaled MFMA per 128-byte K-row
+      // Chunks fq and 4 + fq ARE the instruction's K order: lane group g holds K elements
+      // [16 g, 16 g + 16) in its first four registers and [64 + 16 g, 64 + 16 g + 16) in its last
+      // four, and the scale of K block kb = [32 kb, 32 kb + 32) is read from lane group kb
+      // (measured, tests/test_mx_scaled_gpu.py single-block rows: 32 contiguous bytes per lane
+      // put each half of a lane under another block's scale). So the block-scaled flavour reads
+      // the same fragments and lane (frow, fq) only supplies byte fq of its row's scale word.
       const int c0 = (fq ^ swz) * 16, c1 = ((4 + fq) ^ swz) * 16;
       auto frag8 = [&](const char* r) __attribute__((always_inline)) {
         const i32x4 lo = *(const i32x4*)(r + c0), hi = *(const i32x4*)(r + c1);
@@ -427,7 +493,10 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_tn_kernel(const GemmArgs p) 
 #pragma unroll
       for (int i = 0; i < MR; ++i)
 #pragma unroll
-        for (int j = 0; j < NR; ++j) Mma::step8(acc[i][j], bfr[j], af[i]);
+        for (int j = 0; j < NR; ++j) {
+          if constexpr (SC) Mma::step8s(acc[i][j], bfr[j], af[i], sb[j], sa[i]);
+          else Mma::step8(acc[i][j], bfr[j], af[i]);
+        }
       __builtin_amdgcn_s_setprio(0);
     } else {
 #pragma unroll
@@ -505,20 +574,24 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_tn_kernel(const GemmArgs p) 
 
   const int nk = p.K * esz / ROWB;
   stage(0, 0);
+  load_scales(0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   int cur = 0;
   for (int kt = 0; kt < nk - 1; ++kt) {
+    take_scales();
     if constexpr (ILV) {
       compute_ilv(cur, kt + 1);
     } else {
       stage(cur ^ 1, kt + 1);
+      load_scales(kt + 1);
       compute(cur);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     cur ^= 1;
   }
+  take_scales();
   compute(cur);
 
   // Epilogue: lane holds C[row = .. + frow][col = .. + 4*fq + r], r = 0..3.
@@ -2057,6 +2130,23 @@ hipError_t launch_mx_cfg(const GemmArgs& p, int tile, hipStream_t s) {
     return launch_t8<MmaMX, OUT>(p, s);
   }
   return launch_tiled<MmaMX, OUT>(p, tile, s);
+}
+
+// MX-fp8 with block scales: the tiled kernel, for the codes mxs_offers() lists (gemm.h);
+// gemm_launch has checked the operands and mapped the tile code (mxs_tile_for).
+template <int OUT>
+hipError_t launch_mxs_cfg(const GemmArgs& p, int tile, hipStream_t s) {
+  return dispatch_int<kNumTileCfgs>(tile_slot(tile), [&](auto slot) {
+    constexpr TileCfg c = kTileCfgs[decltype(slot)::value];
+    if constexpr (!mxs_offers(c.code)) {
+      return hipErrorNotSupported;
+    } else {
+      const int tiles = ((p.M + c.rows - 1) / c.rows) * ((p.N + c.cols - 1) / c.cols);
+      hipLaunchKernelGGL((gemm_tn_kernel<MmaMXS, OUT, c.rows, c.cols, c.wm, c.wn, false>),
+                         dim3(tiles), dim3(c.wm * c.wn * 64), 0, s, p);
+      return hipGetLastError();
+    }
+  });
 }
 
 template <int DIN, int DOUT>

@@ -11,9 +11,14 @@
 //    LDS-DMA destination is lane-linear, the swizzle is applied to the per-lane SOURCE address and
 //    undone on the ds_read_b128 (rule 21). Conflict-free for the 16x16 fragment reads.
 //  * MFMA 16x16x32 (bf16/f16), 2x 16x16x32 fp8 per 16 B, 4x 16x16x4 f32 per 16 B, or the
-//    block-scaled 16x16x128 f8f6f4 (MX-fp8, unit scales) that runs at 2x the bf16 rate.
+//    block-scaled 16x16x128 f8f6f4 (MX-fp8) that runs at 2x the bf16 rate: with unit scales, or
+//    with real per-block E8M0 scales (GemmArgs::a_scale / b_scale, the tiled kernel's MmaMXS
+//    flavour, gemm_mxs.hip; quantiser: mx_quant.hip).
 //    Any k-permutation that is identical for A and B leaves the dot product unchanged, which is
-//    what lets one 16-byte ds_read feed every instruction shape.
+//    what lets one 16-byte ds_read feed every instruction shape. For the 16x16x128 instruction
+//    the order used (a lane's chunks fq and 4 + fq of the 128-byte K-row) is also the
+//    instruction's own K order, so its 32-element scale blocks are the format's blocks; the
+//    scale of block kb is supplied by lane group kb (measured; docs/ARCHITECTURE.md).
 //  * Operands are swapped in the MFMA (D = Bt_frag x A_frag) so each lane ends with 4 consecutive
 //    COLUMNS of one C row: the epilogue is one 8-byte (bf16) / 16-byte (f32) store per fragment.
 //  * Grouped-row addressing for A and C: logical row i lives at physical row
@@ -81,6 +86,23 @@ hipError_t gemm_launch(const GemmArgs& p_in, int din, int dout, int tile, int mo
   if (p.c_grp <= 0) { p.c_grp = p.M > 0 ? p.M : 1; p.c_gstride = p.c_grp; }
   // known codes only (the retired families' codes are refused, not rerouted)
   if (tile != TILE_AUTO && tile_slot(tile) < 0) return hipErrorInvalidValue;
+  // MX block scales: both or neither; with them the tiled kernel's scaled flavour or a refusal,
+  // never unit scales in their place
+  if ((p.a_scale != nullptr) != (p.b_scale != nullptr)) return hipErrorInvalidValue;
+  const bool scaled = p.a_scale != nullptr;
+  if (scaled && p.M != 0 && p.N != 0) {
+    if (din != DT_FP8 || mode == GEMM_MODE_GENERIC || (tile != TILE_AUTO && !mxs_offers(tile)) ||
+        p.a_grp != p.M || p.a_table != nullptr || p.flags != nullptr || p.ag_ctas > 0 ||
+        p.ag_mode != 0 || p.ksplit > 1 || !gemm_fast_path_ok(p, din, dout))
+      return hipErrorNotSupported;
+    // one aligned 32-bit word per row and K-tile, rows addressed by 32-bit byte offsets
+    if ((((uintptr_t)p.a_scale | (uintptr_t)p.b_scale) & 3) || p.a_scale_ld % 4 ||
+        p.b_scale_ld % 4 || p.a_scale_ld < p.K / 32 || p.b_scale_ld < p.K / 32 ||
+        (int64_t)p.M * p.a_scale_ld >= (int64_t(1) << 31) ||
+        (int64_t)p.N * p.b_scale_ld >= (int64_t(1) << 31))
+      return hipErrorNotSupported;
+    mode = GEMM_MODE_MX;
+  }
   if (p.M == 0 || p.N == 0) return hipSuccess;
   if (p.ksplit > 1) {
     // K-split: slice j of K columns -> partial j at c + j * M * ldc (the caller sums them). pt4
@@ -156,6 +178,10 @@ hipError_t gemm_launch(const GemmArgs& p_in, int din, int dout, int tile, int mo
   if (p.tile_order && !fast) p.tile_order = 0;
   if (fast) {
     if (tile == TILE_AUTO) tile = choose_tile(p.M, p.N, p.K, din);
+    if (scaled) {  // the tiled shape of that code, among the ones the scaled flavour is built for
+      tile = mxs_tile_for(tile);
+      if (tile < 0) return hipErrorNotSupported;
+    }
     if (p.nsub < 1) p.nsub = 1;
     if (p.tile_order && (p.nshards <= 0 || p.M % p.nshards != 0 || p.nshards % p.nsub != 0 ||
                          (p.M / p.nshards) % tile_rows(tile) != 0)) {
@@ -165,6 +191,7 @@ hipError_t gemm_launch(const GemmArgs& p_in, int din, int dout, int tile, int mo
     }
     if (p.tile_order == 2 && p.N % tile_cols(tile) != 0) p.tile_order = 0;  // whole tiles/shard
     hipError_t e = hipErrorInvalidValue;
+    if (scaled) return launch_fast_mxs(p, dout, tile, s);
     if (din == DT_FP8 && mode == GEMM_MODE_MX) e = launch_fast_mx(p, dout, tile, s);
     else e = launch_fast(p, din, dout, tile, s);
     if (e != hipErrorInvalidValue) return e;

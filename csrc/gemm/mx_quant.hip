@@ -1,0 +1,160 @@
+// MX quantiser for gfx950: x[R, K] (f32 / f16 / bf16) -> q[R, K] OCP e4m3 + s[R, K / 32] E8M0.
+//
+// The format (docs/ARCHITECTURE.md "MX block scaling"): one scale byte s per 32 consecutive K
+// elements of a row, value 2^(s - 127). The rule rounds the scale UP so nothing saturates:
+//   amax = max|x| over the block (fp32);  amax == 0: s = 127, q = 0;  otherwise amax = m 2^ex with
+//   m in [0.5, 1):  e = ex - 9 if m <= 0.875 else ex - 8  (the smallest e with amax / 2^e <= 448),
+//   e clamped to [-127, 127], s = e + 127, q = e4m3_rne(clamp(x 2^-e, -448, 448)).
+// Non-finite input is unspecified. ddlb_amd/ops/mx.py quantize_mx_reference is the specification.
+//
+// A streaming, memory-bound kernel: one 16-byte load per lane (8 16-bit or 4 f32 elements), so 4
+// (8) neighbouring lanes share a block and its amax is a cross-lane max over them (on the integer
+// image of |x|: exact, subnormals included); two v_cvt_pk_fp8_f32 per four elements, one packed
+// 8-byte (4-byte) store per lane, the block's first lane stores the scale byte. A workgroup takes
+// 256 / (vectors per row) rows per pass (one, striding along K, for long rows) and grid-strides
+// over the rows; the grid is sized by the CU count. No LDS.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "gemm.h"
+
+namespace ddlb {
+namespace {
+
+typedef __attribute__((ext_vector_type(4))) unsigned mxq_u32x4;
+constexpr int kMxqThreads = 256;
+
+// The 16 bytes of one load as fp32 values.
+template <int DT> struct MxqIn;
+template <> struct MxqIn<DT_F32> {
+  static constexpr int kElems = 4;
+  static __device__ __forceinline__ void cvt(const mxq_u32x4 v, float* f) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const unsigned u = v[i];  // (a bit_cast of the element lvalue itself reads element 0)
+      f[i] = __builtin_bit_cast(float, u);
+    }
+  }
+};
+template <> struct MxqIn<DT_BF16> {
+  static constexpr int kElems = 8;
+  static __device__ __forceinline__ void cvt(const mxq_u32x4 v, float* f) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      f[2 * i] = __builtin_bit_cast(float, v[i] << 16);
+      f[2 * i + 1] = __builtin_bit_cast(float, v[i] & 0xFFFF0000u);
+    }
+  }
+};
+template <> struct MxqIn<DT_F16> {
+  static constexpr int kElems = 8;
+  static __device__ __forceinline__ void cvt(const mxq_u32x4 v, float* f) {
+    typedef __attribute__((ext_vector_type(2))) _Float16 h2;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const unsigned u = v[i];
+      const h2 h = __builtin_bit_cast(h2, u);
+      f[2 * i] = (float)h.x;
+      f[2 * i + 1] = (float)h.y;
+    }
+  }
+};
+
+template <int DT>
+__global__ __launch_bounds__(kMxqThreads) void mx_quant_kernel(const MxQuantArgs a, int rows_pp) {
+  using In = MxqIn<DT>;
+  constexpr int EPV = In::kElems;   // elements per 16-byte vector
+  constexpr int LPB = 32 / EPV;     // lanes that share a 32-element block
+  constexpr int ESZ = 16 / EPV;
+  const int vpr = a.K / EPV;        // vectors per row: a multiple of 16 (K % 128 == 0)
+  const int tid = threadIdx.x;
+  int r_in = 0, c0 = tid;
+  if (vpr < kMxqThreads) {
+    r_in = tid / vpr;
+    c0 = tid - r_in * vpr;
+  }
+  if (r_in >= rows_pp) return;  // whole blocks' lanes leave together (vpr % LPB == 0)
+  const int64_t row_step = (int64_t)gridDim.x * rows_pp;
+  for (int64_t row = (int64_t)blockIdx.x * rows_pp + r_in; row < a.R; row += row_step) {
+    const char* xr = (const char*)a.x + row * a.ldx * ESZ;
+    char* qr = (char*)a.q + row * a.ldq;
+    uint8_t* sr = a.s + row * a.lds;
+    for (int c = c0; c < vpr; c += kMxqThreads) {  // (lanes of a block share their trip count)
+      const mxq_u32x4 v = *(const mxq_u32x4*)(xr + (int64_t)c * 16);
+      float f[EPV];
+      In::cvt(v, f);
+      unsigned m = 0;  // |x| as an integer: ordered as the floats are
+#pragma unroll
+      for (int i = 0; i < EPV; ++i) {
+        const unsigned b = __builtin_bit_cast(unsigned, f[i]) & 0x7FFFFFFFu;
+        m = b > m ? b : m;
+      }
+#pragma unroll
+      for (int d = 1; d < LPB; d *= 2) {
+        const unsigned o = (unsigned)__shfl_xor((int)m, d);
+        m = o > m ? o : m;
+      }
+      // amax = 1.f 2^(E - 127) = m' 2^(E - 126): m' <= 0.875 <=> fraction <= 0.75. A subnormal
+      // amax (E = 0) clamps to -127 either way.
+      int e = (int)(m >> 23) - 135 + ((m & 0x7FFFFFu) > 0x600000u ? 1 : 0);
+      e = e < -127 ? -127 : (e > 127 ? 127 : e);
+      if (m == 0) e = 0;
+      unsigned out[EPV / 4];
+#pragma unroll
+      for (int i = 0; i < EPV / 4; ++i) {
+        float y[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          y[j] = __builtin_amdgcn_fmed3f(__builtin_ldexpf(f[4 * i + j], -e), -448.f, 448.f);
+        int w = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0, false);
+        w = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], w, true);
+        out[i] = (unsigned)w;
+      }
+      if constexpr (EPV == 8)
+        *(uint2*)(qr + (int64_t)c * 8) = uint2{out[0], out[1]};
+      else
+        *(unsigned*)(qr + (int64_t)c * 4) = out[0];
+      if ((tid & (LPB - 1)) == 0) sr[c / LPB] = (uint8_t)(e + 127);
+    }
+  }
+}
+
+int mxq_cus() {
+  static int n = 0;
+  if (n == 0) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        n <= 0)
+      n = 256;
+  }
+  return n;
+}
+
+}  // namespace
+
+hipError_t mx_quantize_launch(const MxQuantArgs& a, int din, hipStream_t s) {
+  if (din != DT_F32 && din != DT_F16 && din != DT_BF16) return hipErrorInvalidValue;
+  if (a.R < 0 || a.K <= 0 || a.K % 128) return hipErrorInvalidValue;
+  if (a.R == 0) return hipSuccess;
+  const int esz = dtype_size(din);
+  if (a.x == nullptr || a.q == nullptr || a.s == nullptr || a.ldx < a.K || a.ldq < a.K ||
+      a.lds < a.K / 32 || ((uintptr_t)a.x & 15) || (a.ldx * esz) % 16 || ((uintptr_t)a.q & 7) ||
+      a.ldq % 8)
+    return hipErrorInvalidValue;
+  const int vpr = a.K / (16 / esz);
+  const int rows_pp = vpr < kMxqThreads ? kMxqThreads / vpr : 1;
+  // eight 256-thread workgroups fill a CU's wave slots; the rest of the rows by grid stride
+  int64_t grid = ((int64_t)a.R + rows_pp - 1) / rows_pp;
+  const int64_t cap = (int64_t)mxq_cus() * 8;
+  if (grid > cap) grid = cap;
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kMxqThreads), 0, s, a, rows_pp);
+    return hipGetLastError();
+  };
+  if (din == DT_F32) return go(mx_quant_kernel<DT_F32>);
+  if (din == DT_F16) return go(mx_quant_kernel<DT_F16>);
+  return go(mx_quant_kernel<DT_BF16>);
+}
+
+}  // namespace ddlb

@@ -38,6 +38,8 @@ SOURCES = [  # heaviest translation units first (the parallel build's critical p
     "gemm/gemm_f16_f32.hip",
     "gemm/gemm_f32_f32.hip",
     "gemm/gemm_mx.hip",
+    "gemm/gemm_mxs.hip",
+    "gemm/mx_quant.hip",
     "gemm/gemm_generic.hip",
     "gemm/gemm_mfma.hip",
     "runtime/kernels.hip",

@@ -8,7 +8,8 @@ Every shape / dtype / device / alignment / bounds check happens here, on the hos
 kernel launches (a bad launch can fault every GPU of the node).
 
 dtypes: bf16 -> bf16|f32, f16 -> f16|f32, f32 -> f32 (exact f32 MFMA), float8_e4m3fn -> bf16|f16|f32
-(``mx=True``: block-scaled MX-fp8 MFMA at 2x the bf16 rate, unit scales), f64 (generic kernel).
+(``mode="mx"``: block-scaled MX-fp8 MFMA at 2x the bf16 rate; unit scales, or real per-block E8M0
+scales with ``a_scale`` / ``w_scale``, see :mod:`ddlb_amd.ops.mx`), f64 (generic kernel).
 """
 
 from __future__ import annotations
@@ -113,18 +114,65 @@ def split_k_factor(M: int, N: int, K: int, esz: int, ncu: int = 0) -> int:
     return 1
 
 
+SCALED_TILES = ("256x128", "128x256", "128x128", "256x128w4")  # gemm.h mxs_offers()
+
+
+def _check_scales(a, w, a_scale, w_scale, M, tile, mode, a_grp, ksplit):
+    """Every refusal of the block-scaled GEMM, before anything is launched."""
+    import torch
+
+    if (a_scale is None) != (w_scale is None):
+        raise ValueError("a_scale and w_scale go together: pass both or neither")
+    if a.dtype != torch.float8_e4m3fn:
+        raise TypeError(f"block scales need float8_e4m3fn operands, not {a.dtype}")
+    if mode not in ("auto", "mx"):
+        raise ValueError(f"block scales run the MX kernel (mode auto / mx), not mode={mode!r}")
+    if tile != "auto" and tile not in SCALED_TILES:
+        raise ValueError(f"block scales are offered for tile auto / {SCALED_TILES}, not "
+                         f"{tile!r} (the ping-pong kernels t8 / pt8 / t4 / pt4 take unit scales)")
+    if a_grp not in (0, M):
+        raise ValueError("block scales need plain A rows (no grouped A rows)")
+    if ksplit > 1:
+        raise ValueError("block scales do not combine with a K-split")
+    K = a.shape[1]
+    if K % 128:
+        raise ValueError(f"block scales need K % 128 == 0 (K = {K})")
+    for name, sc, rows in (("a_scale", a_scale, a.shape[0]), ("w_scale", w_scale, w.shape[0])):
+        if not isinstance(sc, torch.Tensor) or sc.dtype != torch.uint8:
+            raise TypeError(f"{name} must be a uint8 tensor of E8M0 bytes")
+        if sc.device != a.device:
+            raise ValueError(f"{name} is on {sc.device}, the operands on {a.device}")
+        if tuple(sc.shape) != (rows, K // 32):
+            raise ValueError(f"{name} must have shape {(rows, K // 32)}, not {tuple(sc.shape)}")
+        if sc.stride(1) != 1 or sc.stride(0) % 4 or sc.stride(0) < K // 32:
+            raise ValueError(f"{name} needs unit inner stride and a row stride that is a "
+                             f"multiple of 4 (strides {tuple(sc.stride())})")
+        if sc.data_ptr() % 4:
+            raise ValueError(f"{name} must start at a 4-byte-aligned address")
+        if rows * sc.stride(0) >= 2 ** 31:
+            raise ValueError(f"{name} spans 2 GiB or more")
+
+
 def gemm(a, w, out=None, *, out_dtype=None, tile: str = "auto", mode: str = "auto",
          M: Optional[int] = None, a_grp: int = 0, a_gstride: int = 0, c_grp: int = 0,
-         c_gstride: int = 0, stream=None, act: str = "none", ksplit: int = 0):
+         c_gstride: int = 0, stream=None, act: str = "none", ksplit: int = 0,
+         a_scale=None, w_scale=None):
     """``out[:M] = act(a[:M] @ w.T)`` on the current HIP stream (grouped-row addressing and a
     fused epilogue activation — none / gelu (tanh) / relu / silu — optional). ``ksplit``: 0 =
     auto (:func:`split_k_factor` for plain-row auto-tile GEMMs with no activation and a dense
     output), 1 = never, S > 1 = S slices. A pt4 split runs one launch over (slice, tile) pairs
     into f32 partials, summed in slice order and rounded once by the reduce kernel (0.1122 ms on
-    8192 x 1024 x 8192 bf16, ``profiles/r05/r5_14_*``)."""
+    8192 x 1024 x 8192 bf16, ``profiles/r05/r5_14_*``).
+
+    ``a_scale`` / ``w_scale`` (both or neither; fp8 operands): MX block scales, ``uint8``
+    ``[rows, K / 32]`` E8M0 bytes (value ``2^(s - 127)`` for 32 consecutive K elements of a row,
+    :mod:`ddlb_amd.ops.mx`). They run the block-scaled flavour of the tiled kernel (tiles
+    :data:`SCALED_TILES`, ``auto`` picks among them; plain A rows, no K-split); anything else
+    raises here, never a launch with unit scales in their place."""
     import torch
 
     C = load()
+    scaled = a_scale is not None or w_scale is not None
     if out is None:
         rows = M if M is not None else a.shape[0]
         out = torch.empty((rows, w.shape[0]), dtype=out_dtype or default_out_dtype(a.dtype),
@@ -146,6 +194,18 @@ def gemm(a, w, out=None, *, out_dtype=None, tile: str = "auto", mode: str = "aut
     plain = (a_grp in (0, M) and c_grp in (0, M) and ACTS[act] == 0 and out.stride(0) == N
              and mode != "generic" and a.dtype != torch.float64)
     S = int(ksplit)
+    if scaled:
+        _check_scales(a, w, a_scale, w_scale, M, tile, mode, a_grp, S)
+        if M and N and not C.gemm_fast_path_ok(a.data_ptr(), w.data_ptr(), out.data_ptr(),
+                                               a.stride(0), w.stride(0), out.stride(0), M, N, K,
+                                               DT_FP8, dtype_code(out.dtype)):
+            raise ValueError("block scales need the MFMA fast path: 16-byte-aligned operand "
+                             "rows, 8-byte-aligned output rows")
+        C.gemm(a.data_ptr(), w.data_ptr(), out.data_ptr(), a.stride(0), w.stride(0),
+               out.stride(0), M, N, K, DT_FP8, dtype_code(out.dtype), TILES[tile], MODES["mx"],
+               0, 0, c_grp, c_gstride, s, ACTS[act], 1, a_scale.data_ptr(), w_scale.data_ptr(),
+               a_scale.stride(0), w_scale.stride(0))
+        return out
     if S == 0:
         S = split_k_factor(M, N, K, a.element_size()) if plain and tile == "auto" else 1
     if S > 1:

@@ -55,3 +55,50 @@ class GemmBackend:
         if out is not None:
             return torch.matmul(a, w, out=out)
         return torch.matmul(a, w)
+
+
+QUANT_CHOICES = ["none", "mx"]
+
+
+class MxQuantGemm:
+    """``quant=mx`` of the compute_only slots: a bf16 / f16 activation through the fp8 matrix
+    pipe, as an fp8 linear layer runs it. The ``[n, k]`` weight is quantised once at set-up
+    (:func:`ddlb_amd.ops.mx.quantize_mx`); every call quantises the activation and runs the
+    block-scaled GEMM, both on the clock. Output in the benchmark dtype. HIP kernels only: it
+    raises at construction on a CPU device, with ``gemm=torch`` or for another dtype."""
+
+    def __init__(self, backend: GemmBackend, k: int):
+        if backend.dtype_name not in ("bfloat16", "float16"):
+            raise ValueError(f"quant=mx quantises bfloat16 or float16 inputs, not "
+                             f"{backend.dtype_name}")
+        if backend.device.type != "cuda":
+            raise ValueError("quant=mx needs a ROCm GPU (the quantiser and the scaled GEMM are "
+                             "HIP kernels)")
+        if backend.choice != "hip":
+            raise ValueError(f"quant=mx runs the hip GEMM, not gemm={backend.choice}")
+        if k % 128:
+            raise ValueError(f"quant=mx needs the GEMM's K ({k}) to be a multiple of 128")
+        from ddlb_amd.ops import gemm as _g
+        from ddlb_amd.ops import mx as _mx
+
+        self._g, self._mx = _g, _mx
+        self.wq = self.ws = None
+
+    def prepare_weight(self, b):
+        """``b`` is ``[k, n]``; quantised as the ``[n, k]`` weight the kernel reads."""
+        self.wq, self.ws = self._mx.quantize_mx(b.t().contiguous())
+        return self.wq
+
+    def __call__(self, a, out):
+        aq, a_s = self._mx.quantize_mx(a)
+        return self._g.gemm(aq, self.wq, out=out, a_scale=a_s, w_scale=self.ws)
+
+    def expected(self, a, b):
+        """fp32 product of the DEQUANTISED reference-quantised operands: what the scaled GEMM
+        is asked to compute. Against the unquantised product the format's own error (up to 1.85
+        at k = 1024 with U[-1, 1) inputs) exceeds DDLB's ``atol = 1e-3 k``, so that rule would
+        judge the number format and not the kernels."""
+        ref = self._mx.quantize_mx_reference
+        a_dq = self._mx.dequantize_mx(*ref(a))
+        w_dq = self._mx.dequantize_mx(*ref(b.t().contiguous()))
+        return a_dq @ w_dq.t()

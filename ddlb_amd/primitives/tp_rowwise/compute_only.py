@@ -3,18 +3,21 @@
 Not present in the reference (``ddlb/benchmark.py:51-55`` registers none for tp_rowwise); added
 so the GEMM share of the rowwise pipelines can be measured on its own. ``size=sharded`` runs
 ``[m, k/d] x [k/d, n]`` (this rank's real work); ``unsharded`` runs the full ``[m, k] x [k, n]``.
-Validation compares against the matching fp32 product.
+Validation compares against the matching fp32 product. ``quant=mx``: the activation is quantised
+to MX-fp8 inside the timed step and multiplied by the block-scaled GEMM, validated against the
+product of the dequantised operands (see the columnwise slot and :class:`MxQuantGemm`).
 """
 
 from __future__ import annotations
 
-from ddlb_amd.primitives.gemm_select import GemmBackend
+from ddlb_amd.primitives.gemm_select import QUANT_CHOICES, GemmBackend, MxQuantGemm
 from ddlb_amd.primitives.tp_rowwise.base import TPRowwise
 
 
 class ComputeOnlyTPRowwise(TPRowwise):
-    DEFAULT_OPTIONS = {"size": "sharded", "gemm": "auto"}
-    ALLOWED_VALUES = {"size": ["sharded", "unsharded"], "gemm": ["auto", "hip", "torch", "torch_nt"]}
+    DEFAULT_OPTIONS = {"size": "sharded", "gemm": "auto", "quant": "none"}
+    ALLOWED_VALUES = {"size": ["sharded", "unsharded"], "gemm": ["auto", "hip", "torch", "torch_nt"],
+                      "quant": QUANT_CHOICES}
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
@@ -25,11 +28,18 @@ class ComputeOnlyTPRowwise(TPRowwise):
         else:
             self.a_in, b = self.A, self.B
         self._b_ref = b
-        self.w = self.gemm.prepare_weight(b)
+        self.mx = MxQuantGemm(self.gemm, b.shape[0]) if self.options["quant"] == "mx" else None
+        self.w = (self.mx or self.gemm).prepare_weight(b)
         self.out = self.gemm.alloc_out(self.m, self.n)
 
     def run(self):
+        if self.mx is not None:
+            return self.mx(self.a_in, self.out)
         return self.gemm(self.a_in, self.w, self.out)
 
     def expected(self):
+        """fp32 reference; with ``quant=mx`` the product of the DEQUANTISED reference-quantised
+        operands (:meth:`MxQuantGemm.expected` says why)."""
+        if self.mx is not None:
+            return self.mx.expected(self.a_in, self._b_ref)
         return self._ref_matmul(self.a_in, self._b_ref)

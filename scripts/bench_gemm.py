@@ -46,8 +46,11 @@ def timeit(fn, iters, warm=3):
 def main():
     import torch
 
-    from ddlb_amd.ops.gemm import gemm
+    from ddlb_amd.ops import load
+    from ddlb_amd.ops.gemm import SCALED_TILES, gemm
+    from ddlb_amd.ops.mx import quantize_mx
 
+    C = load()
     p = argparse.ArgumentParser()
     p.add_argument("--dtype", default="bfloat16")
     p.add_argument("--rounds", type=int, default=5)
@@ -57,6 +60,11 @@ def main():
     p.add_argument("--shapes", default="all")
     p.add_argument("--json", default=None)
     p.add_argument("--check", action="store_true", help="tight numerics check first")
+    p.add_argument("--scaled", action="store_true",
+                   help="fp8, mode mx: a native[tile,mx+scales] variant (real E8M0 block scales, "
+                        "all 127 so --check still holds) beside each native[tile,mx] whose tile "
+                        "the scaled kernel offers, and a quantize_mx row (bf16 [M, K] -> e4m3 + "
+                        "scales) beside a copy moving the same bytes")
     a = p.parse_args()
     dt = getattr(torch, a.dtype)
     g = torch.Generator(device="cuda")
@@ -87,6 +95,23 @@ def main():
             for mode in a.modes.split(","):
                 variants[f"native[{t},{mode}]"] = (lambda t=t, mode=mode: gemm(A, W, out, tile=t,
                                                                                mode=mode))
+                if a.scaled and mode == "mx" and dt == torch.float8_e4m3fn and (
+                        t == "auto" or t in SCALED_TILES):
+                    sa = torch.full((M, K // 32), 127, dtype=torch.uint8, device="cuda")
+                    sw = torch.full((N, K // 32), 127, dtype=torch.uint8, device="cuda")
+                    variants[f"native[{t},mx+scales]"] = (
+                        lambda t=t, sa=sa, sw=sw: gemm(A, W, out, tile=t, a_scale=sa, w_scale=sw))
+        extra = {}  # name -> (callable, bytes moved)
+        if a.scaled:
+            X = (torch.rand((M, K), generator=g, device="cuda") * 2 - 1).to(torch.bfloat16)
+            moved = M * K * 2 + M * K + M * K // 32
+            half = moved // 2 // 16 * 16
+            src = torch.empty(half, dtype=torch.uint8, device="cuda")
+            dst = torch.empty(half, dtype=torch.uint8, device="cuda")
+            st = torch.cuda.current_stream().cuda_stream
+            extra["quantize_mx[bf16]"] = (lambda: quantize_mx(X), moved)
+            extra["copy[same bytes]"] = (
+                lambda: C.copy(dst.data_ptr(), src.data_ptr(), half, 0, st), 2 * half)
         if a.check:  # tight numerics of every native variant before timing it
             ref = A.float() @ W.float().t()
             bound = 2.0 ** -7 * float(ref.abs().max()) + K * 2.0 ** -12
@@ -100,15 +125,22 @@ def main():
                 print(f"  check {k:24s} max|err| {err:.4g} (bound {bound:.4g}) "
                       f"{'ok' if err <= bound else 'FAIL'}")
             del ref
-        times = {k: [] for k in variants}
+        times = {k: [] for k in list(variants) + list(extra)}
         for _ in range(a.rounds):
             for k, fn in variants.items():
+                times[k].append(timeit(fn, a.iters))
+            for k, (fn, _) in extra.items():
                 times[k].append(timeit(fn, a.iters))
         flop = 2.0 * M * N * K
         row = {"M": M, "N": N, "K": K, "dtype": a.dtype, "note": note, "variants": {}}
         print(f"\n{M}x{N}x{K} {a.dtype}  ({note})")
         for k, ts in times.items():
             med = statistics.median(ts)
+            if k in extra:  # a streaming kernel: bytes moved (read + written) per second
+                gbs = extra[k][1] / (med * 1e-3) / 1e9
+                row["variants"][k] = {"ms_median": med, "ms_min": min(ts), "gb_per_s": gbs}
+                print(f"  {k:28s} {med:8.4f} ms  {gbs:8.1f} GB/s")
+                continue
             tf = flop / (med * 1e-3) / 1e12
             row["variants"][k] = {"ms_median": med, "ms_min": min(ts), "tflops": tf}
             print(f"  {k:28s} {med:8.4f} ms  {tf:8.1f} TFLOP/s")
