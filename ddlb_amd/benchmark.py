@@ -280,8 +280,9 @@ class PrimitiveBenchmarkRunner:
 
     def _next_init_method(self) -> str:
         """Rendezvous of the next child process group. Rank 0 binds a currently free port and,
-        when there are several ranks, publishes it through a small TCPStore the parent
-        processes share (created once at the base port; no GPU involved), so every rank's
+        when there are several ranks, publishes it through a store the parent processes share
+        (torchrun's own at MASTER_PORT when its agent serves one, else a small TCPStore created
+        once at the base port; no GPU involved), so every rank's
         child dials the same, actually free port (a fixed port sequence collided with ephemeral
         ports of earlier children's sockets: EADDRINUSE)."""
         idx = PrimitiveBenchmarkRunner._child_counter
@@ -294,10 +295,19 @@ class PrimitiveBenchmarkRunner:
             from torch.distributed import TCPStore
 
             if PrimitiveBenchmarkRunner._store is None:
-                PrimitiveBenchmarkRunner._store = TCPStore(
-                    get_master_addr(), get_master_port(), world, rank == 0,
-                    timeout=datetime.timedelta(seconds=self.child_timeout_s))
-            key = f"ddlb_child_port_{idx}"
+                timeout = datetime.timedelta(seconds=self.child_timeout_s)
+                if (os.environ.get("TORCHELASTIC_USE_AGENT_STORE") == "True"
+                        and "MASTER_PORT" in os.environ):
+                    # torchrun's agent already serves a store at MASTER_PORT: join it as a
+                    # client. A server of our own at MASTER_PORT + 1 failed with EADDRINUSE
+                    # whenever that port was some other socket's ephemeral port.
+                    PrimitiveBenchmarkRunner._store = TCPStore(
+                        get_master_addr(), int(os.environ["MASTER_PORT"]), None, False,
+                        timeout=timeout)
+                else:
+                    PrimitiveBenchmarkRunner._store = TCPStore(
+                        get_master_addr(), get_master_port(), world, rank == 0, timeout=timeout)
+            key = f"ddlb_child_port_{os.environ.get('TORCHELASTIC_RESTART_COUNT', '0')}_{idx}"
             if rank == 0:
                 PrimitiveBenchmarkRunner._store.set(key, str(port))
             else:

@@ -9,9 +9,11 @@ The quantisation rule rounds the scale UP, so nothing saturates. Per block, in f
 ``amax = max|x|``; ``amax == 0`` gives ``s = 127`` and ``q = 0``; otherwise ``amax = m 2^ex`` with
 ``m`` in [0.5, 1) and ``e = ex - 9`` if ``m <= 0.875`` else ``ex - 8`` (the smallest ``e`` with
 ``amax / 2^e <= 448``, the largest e4m3 value), clamped to [-127, 127]; ``s = e + 127`` and
-``q = e4m3_rne(clamp(x 2^-e, -448, 448))``. ``s = 255`` is never produced. Non-finite input is
-unspecified. (The OCP "floor" rule, ``e = floor(log2 amax) - 8``, would clamp every element
-above 448 2^e: 11 % of the elements of U[-1, 1) data.)
+``q = e4m3_rne(clamp(x 2^-e, -448, 448))``. ``s = 255`` is never produced. The sign of a zero is
+kept: -0, and a negative value that rounds to zero, give the byte 0x80 (kernel and reference
+agree byte for byte, ``tests/test_mx_extremes_gpu.py``). Non-finite input is unspecified. (The
+OCP "floor" rule, ``e = floor(log2 amax) - 8``, would clamp every element above 448 2^e: 11 % of
+the elements of U[-1, 1) data.)
 
 :func:`quantize_mx_reference` and :func:`dequantize_mx` are pure torch, run on any device, and are
 the specification; :func:`quantize_mx` is the HIP kernel (``csrc/gemm/mx_quant.hip``).
@@ -65,7 +67,12 @@ def quantize_mx_reference(x):
 
 
 def dequantize_mx(q, s):
-    """``q [R, K]`` e4m3 and ``s [R, K/32]`` E8M0 bytes -> the float32 values they stand for."""
+    """``q [R, K]`` e4m3 and ``s [R, K/32]`` E8M0 bytes -> the float32 values they stand for.
+    fp32 cannot hold every one of them: at ``s = 254`` an element with ``|q| >= 2`` is ``inf``
+    here (``2 * 2^127``), while the block-scaled MFMA, which adds the two scale exponents before
+    it rounds, returns the finite product it has with a small partner scale. The scaled GEMM is
+    exact over the whole byte range 0..254 (measured against an fp64 dequantisation,
+    ``tests/test_mx_extremes_gpu.py``)."""
     import torch
 
     R, K = q.shape

@@ -59,3 +59,40 @@ def test_reduce_sum_f32_sources(dtype, nsrc, count):
         assert torch.isnan(out[count:].float()).all()
     with pytest.raises(RuntimeError):  # f32 sources only, 16-bit destinations only
         C.reduce_sum(out.data_ptr(), [slab[0].data_ptr()], count, DT[dtype], s, DT[dtype] ^ 3)
+
+
+def _int_slab(nsrc, pad, dtype, seed):
+    gen = torch.Generator(device="cuda").manual_seed(seed)
+    return torch.randint(-3, 4, (nsrc, pad), generator=gen, device="cuda").float().to(dtype)
+
+
+@pytest.mark.parametrize("count", [8, 1003, 4099])
+def test_reduce_sum_exact(count):
+    """Integer-valued sources in -3..3: every partial sum is exact, so the result is the sum
+    rounded once (not at all here: |sum| <= 48), compared bit for bit. Every source count of the
+    same-dtype form (1, the unrolled 2..8, the runtime-count kernel up to 16) and of the
+    f32-source form (1..9); a vector body with and without a scalar tail; the NaN-filled
+    elements after ``count`` stay NaN."""
+    from ddlb_amd.ops import load
+
+    C = load()
+    s = torch.cuda.current_stream().cuda_stream
+    pad = (count + 7) // 8 * 8 + 8
+    for dtype in DT:
+        slab = _int_slab(16, pad, dtype, count)
+        for nsrc in range(1, 17):
+            out = torch.full((pad,), float("nan"), device="cuda", dtype=dtype)
+            C.reduce_sum(out.data_ptr(), [slab[i].data_ptr() for i in range(nsrc)], count,
+                         DT[dtype], s)
+            want = slab[:nsrc, :count].double().sum(dim=0).float().to(dtype)
+            assert torch.equal(out[:count], want), (dtype, nsrc)
+            assert bool(torch.isnan(out[count:].float()).all()), (dtype, nsrc)
+    slab = _int_slab(9, pad, torch.float32, count + 1)
+    for dtype in (torch.float16, torch.bfloat16):
+        for nsrc in range(1, 10):
+            out = torch.full((pad,), float("nan"), device="cuda", dtype=dtype)
+            C.reduce_sum(out.data_ptr(), [slab[i].data_ptr() for i in range(nsrc)], count,
+                         DT[dtype], s, DT[torch.float32])
+            want = slab[:nsrc, :count].double().sum(dim=0).float().to(dtype)
+            assert torch.equal(out[:count], want), (dtype, nsrc)
+            assert bool(torch.isnan(out[count:].float()).all()), (dtype, nsrc)

@@ -124,6 +124,42 @@ def test_cli_torchrun_two_ranks(tmp_path):
         assert row["world_size"] == "2" and row["valid"] == "True", row
 
 
+def test_cli_torchrun_port_above_master_taken(tmp_path):
+    """The parents of the per-child process groups share torchrun's own store: no second fixed
+    port has to be free (a server at MASTER_PORT + 1 died with EADDRINUSE when that port was
+    another socket's)."""
+    import socket
+
+    from conftest import free_port
+
+    while True:
+        port = free_port()
+        taken = socket.socket()
+        try:
+            taken.bind(("127.0.0.1", port + 1))
+            taken.listen(1)
+            break
+        except OSError:
+            taken.close()
+    try:
+        out = tmp_path / "tp_{timestamp}.csv"
+        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
+               "--master-addr", "127.0.0.1", "--master-port", str(port), "-m", "ddlb_amd",
+               "--primitive", "tp_rowwise", "-m", "64", "-n", "16", "-k", "32", "--dtype",
+               "float32", "--num-iterations", "2", "--num-warmups", "1", "--profile-iterations",
+               "1", "--impl", "compute_only;size=sharded", "--output-csv", str(out)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=_env(),
+                           cwd=ROOT)
+    finally:
+        taken.close()
+    assert r.returncode == 0, r.stderr[-4000:]
+    files = list(tmp_path.glob("tp_*.csv"))
+    assert len(files) == 1, r.stdout[-3000:]
+    with open(files[0], newline="") as f:
+        rows = list(csv.DictReader(f))
+    assert len(rows) == 1 and rows[0]["world_size"] == "2" and rows[0]["valid"] == "True"
+
+
 def test_json_script_entry(tmp_path):
     cfg = _config(tmp_path, {"compute_only": [{"size": "unsharded"}]})
     p = tmp_path / "cfg.json"
