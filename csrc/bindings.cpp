@@ -164,6 +164,23 @@ PYBIND11_MODULE(_C, m) {
         },
         py::arg("x"), py::arg("q"), py::arg("s"), py::arg("ldx"), py::arg("ldq"),
         py::arg("lds"), py::arg("R"), py::arg("K"), py::arg("din"), py::arg("stream") = 0);
+  m.def("mxfp4_quantize",  // the same -> q[R, K / 2] E2M1 nibble pairs (ldq in bytes) + s
+        [](uintptr_t x, uintptr_t q, uintptr_t sc, int64_t ldx, int64_t ldq, int64_t lds, int R,
+           int K, int din, uintptr_t stream) {
+          MxQuantArgs a;
+          a.x = (const void*)x; a.q = (void*)q; a.s = (uint8_t*)sc;
+          a.ldx = ldx; a.ldq = ldq; a.lds = lds;
+          a.R = R; a.K = K;
+          check(mxfp4_quantize_launch(a, din, (hipStream_t)stream), "mxfp4_quantize");
+        },
+        py::arg("x"), py::arg("q"), py::arg("s"), py::arg("ldx"), py::arg("ldq"),
+        py::arg("lds"), py::arg("R"), py::arg("K"), py::arg("din"), py::arg("stream") = 0);
+  m.attr("MX4_TILES") = [] {  // tile codes the block-scaled fp4 GEMM is built for
+    std::vector<int> v;
+    for (int i = 0; i < kNumTileCfgs; ++i)
+      if (mx4_offers(kTileCfgs[i].code)) v.push_back(kTileCfgs[i].code);
+    return v;
+  }();
   m.attr("MXS_TILES") = [] {  // tile codes the block-scaled GEMM is built for
     std::vector<int> v;
     for (int i = 0; i < kNumTileCfgs; ++i)

@@ -6,7 +6,10 @@
 namespace ddlb {
 
 // dtype codes shared with Python (ddlb_amd/ops/_dtypes.py)
-enum DType : int { DT_F32 = 0, DT_F16 = 1, DT_BF16 = 2, DT_FP8 = 3, DT_F64 = 4, DT_U8 = 5 };
+// DT_FP4: OCP E2M1, two elements per byte (element 2j in the low nibble of byte j); dtype_size()
+// is 0 for it, a row of K elements is K / 2 bytes.
+enum DType : int { DT_F32 = 0, DT_F16 = 1, DT_BF16 = 2, DT_FP8 = 3, DT_F64 = 4, DT_U8 = 5,
+                   DT_FP4 = 6 };
 inline int dtype_size(int dt) {
   switch (dt) {
     case DT_F32: return 4;
@@ -78,6 +81,12 @@ constexpr int mxs_tile_for(int tile) {
       return kTileCfgs[j].code;
   return TILE_256x128;
 }
+
+// Tile codes of the block-scaled fp4 flavour (MmaMX4S, gemm_mx4.hip): the set the fp8 scaled
+// flavour offers, `auto` mapped the same way (mxs_tile_for). Both 256x256 forms stay out as they
+// do for fp8: an instantiation that spills to scratch is not offered (TILE_256x256, 2x4 waves:
+// 140 bytes per lane; TILE_256x256_W4: 228; docs/ARCHITECTURE.md has the register table).
+constexpr bool mx4_offers(int tile) { return mxs_offers(tile); }
 
 constexpr bool tile_cfgs_distinct() {
   for (int i = 0; i < kNumTileCfgs; ++i)
@@ -158,6 +167,9 @@ struct GemmArgs {
   // per 32 consecutive K elements of a row, row-major [rows, K / 32] with a row stride of
   // a_scale_ld / b_scale_ld BYTES (a multiple of 4, base 4-byte aligned), so the four scales of a
   // row's 128-byte K-tile are one aligned 32-bit word. Null: unit scales, the kernels above.
+  // DT_FP4 operands (E2M1, lda / ldb in ELEMENTS and even, K % 256 == 0) always carry scales, in
+  // the same layout; base and row stride are then multiples of 8, so the eight scales of a row's
+  // 128-byte K-tile (256 elements) are one aligned 64-bit load.
   const uint8_t* a_scale = nullptr;
   const uint8_t* b_scale = nullptr;
   int64_t a_scale_ld = 0, b_scale_ld = 0;
@@ -188,6 +200,10 @@ struct MxQuantArgs {
   int R = 0, K = 0;
 };
 hipError_t mx_quantize_launch(const MxQuantArgs& a, int din, hipStream_t s);
+// The MXFP4 flavour: q[R, K / 2] bytes of E2M1 nibble pairs (element 2j in the low nibble of byte
+// j; rows ldq BYTES apart, 4-byte aligned), the same scale array; the rule with 6 in place of 448
+// (e = ex - 3 if m <= 0.75 else ex - 2), ties to the even code. K % 256 == 0.
+hipError_t mxfp4_quantize_launch(const MxQuantArgs& a, int din, hipStream_t s);
 
 hipError_t gemm_launch(const GemmArgs& p, int din, int dout, int tile, int mode, hipStream_t s);
 bool gemm_fast_path_ok(const GemmArgs& p, int din, int dout);

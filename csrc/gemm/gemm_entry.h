@@ -15,6 +15,8 @@ hipError_t launch_fast_f32_f32(const GemmArgs& p, int tile, hipStream_t s);
 hipError_t launch_fast_mx(const GemmArgs& p, int dout, int tile, hipStream_t s);
 // MX-fp8 with block scales (GemmArgs::a_scale / b_scale): the tiled kernel, offered tiles only
 hipError_t launch_fast_mxs(const GemmArgs& p, int dout, int tile, hipStream_t s);
+// MXFP4 with block scales (DT_FP4 operands): the tiled kernel, offered tiles only
+hipError_t launch_fast_mx4(const GemmArgs& p, int dout, int tile, hipStream_t s);
 hipError_t launch_generic(const GemmArgs& p, int din, int dout, hipStream_t s);
 
 // Dispatch of the fast (MFMA) family by dtype pair; hipErrorInvalidValue if not provided.

@@ -18,6 +18,7 @@ namespace {
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(8))) int i32x8;
+typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 
@@ -122,6 +123,24 @@ struct MmaMXS {
     acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(b, a, acc, 0, 0, 0, sb, 0, sa);
   }
 };
+// MXFP4 with block scales (kFp4): E2M1 operands, format code 4 for both, which reads the first FOUR
+// registers of each operand (16 bytes = 32 elements per lane) and runs at twice the MX-fp8 rate.
+// A 128-byte K-row holds 256 elements, so it takes two of them: chunk fq with byte fq of the
+// row's first scale word, chunk 4 + fq with byte fq of the second. Lane group g = lane >> 4 holds
+// one whole 32-element block in its 16 bytes and block g's scale is read from lane group g
+// (measured: see the comment above frag8 in the tiled kernel). Tiled kernel only.
+struct MmaMX4S {
+  static constexpr int kElem = 1, kMfma = 2;  // (kElem: the kernel addresses operand BYTES)
+  static constexpr bool kPair = true, kScaled = true, kFp4 = true;
+  static __device__ __forceinline__ void step4s(f32x4& acc, const i32x4& b, const i32x4& a,
+                                                int sb, int sa) {
+    const i32x8 b8 = {b.x, b.y, b.z, b.w, 0, 0, 0, 0}, a8 = {a.x, a.y, a.z, a.w, 0, 0, 0, 0};
+    acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(b8, a8, acc, 4, 4, 0, sb, 0, sa);
+  }
+};
+template <class Mma, class = void> struct is_fp4 : std::false_type {};
+template <class Mma> struct is_fp4<Mma, std::void_t<decltype(Mma::kFp4)>>
+    : std::integral_constant<bool, Mma::kFp4> {};
 template <class Mma, class = void> struct is_pair : std::false_type {};
 template <class Mma> struct is_pair<Mma, std::void_t<decltype(Mma::kPair)>>
     : std::integral_constant<bool, Mma::kPair> {};
@@ -439,11 +458,13 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_tn_kernel(const GemmArgs p) 
   // memory (no LDS traffic) beside the DMA of the K-tile they belong to and first touched after
   // the vmcnt(0) that ends the iteration: an ordinary load's result used while an LDS-DMA is in
   // flight would make the compiler drain the DMA there. Rows are clamped as the data rows are.
-  constexpr bool SC = is_scaled<Mma>::value;
-  constexpr int NSA = SC ? MR : 1, NSB = SC ? NR : 1;
-  unsigned sa_off[NSA], sb_off[NSB];  // byte offset of each fragment's scale row
-  unsigned sa_w[NSA], sb_w[NSB];      // scale words in flight (the K-tile being staged)
-  int sa[NSA], sb[NSB];               // this K-tile's scale byte
+  // MmaMX4S: a K-tile row is 256 fp4 elements, eight scale bytes, two words (one 64-bit load);
+  // lane (frow, fq) takes byte fq of each: blocks 8 kt + fq and 8 kt + 4 + fq, one per MFMA.
+  constexpr bool SC = is_scaled<Mma>::value, F4 = is_fp4<Mma>::value;
+  constexpr int NSA = SC ? MR : 1, NSB = SC ? NR : 1, NSW = F4 ? 2 : 1;
+  unsigned sa_off[NSA], sb_off[NSB];        // byte offset of each fragment's scale row
+  unsigned sa_w[NSA][NSW], sb_w[NSB][NSW];  // scale words in flight (the K-tile being staged)
+  int sa[NSA][NSW], sb[NSB][NSW];           // this K-tile's scale byte(s)
   if constexpr (SC) {
 #pragma unroll
     for (int i = 0; i < MR; ++i) {
@@ -460,12 +481,27 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_tn_kernel(const GemmArgs p) 
   }
   auto load_scales = [&](int kt) __attribute__((always_inline)) {
     if constexpr (SC) {
-      const GLB_AS char* ga = (const GLB_AS char*)p.a_scale + kt * 4;
-      const GLB_AS char* gb = (const GLB_AS char*)p.b_scale + kt * 4;
+      const GLB_AS char* ga = (const GLB_AS char*)p.a_scale + kt * (4 * NSW);
+      const GLB_AS char* gb = (const GLB_AS char*)p.b_scale + kt * (4 * NSW);
+      if constexpr (F4) {
 #pragma unroll
-      for (int i = 0; i < MR; ++i) sa_w[i] = *(const GLB_AS unsigned*)(ga + sa_off[i]);
+        for (int i = 0; i < MR; ++i) {
+          const u32x2 w = *(const GLB_AS u32x2*)(ga + sa_off[i]);
+          sa_w[i][0] = w.x;
+          sa_w[i][NSW - 1] = w.y;
+        }
 #pragma unroll
-      for (int j = 0; j < NR; ++j) sb_w[j] = *(const GLB_AS unsigned*)(gb + sb_off[j]);
+        for (int j = 0; j < NR; ++j) {
+          const u32x2 w = *(const GLB_AS u32x2*)(gb + sb_off[j]);
+          sb_w[j][0] = w.x;
+          sb_w[j][NSW - 1] = w.y;
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < MR; ++i) sa_w[i][0] = *(const GLB_AS unsigned*)(ga + sa_off[i]);
+#pragma unroll
+        for (int j = 0; j < NR; ++j) sb_w[j][0] = *(const GLB_AS unsigned*)(gb + sb_off[j]);
+      }
     }
   };
   auto take_scales = [&]() __attribute__((always_inline)) {
@@ -473,9 +509,13 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_tn_kernel(const GemmArgs p) 
       // (the fences keep these uses between the barrier and the next stage's DMA)
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int i = 0; i < MR; ++i) sa[i] = (int)__builtin_amdgcn_ubfe(sa_w[i], fq * 8, 8);
+      for (int i = 0; i < MR; ++i)
 #pragma unroll
-      for (int j = 0; j < NR; ++j) sb[j] = (int)__builtin_amdgcn_ubfe(sb_w[j], fq * 8, 8);
+        for (int w = 0; w < NSW; ++w) sa[i][w] = (int)__builtin_amdgcn_ubfe(sa_w[i][w], fq * 8, 8);
+#pragma unroll
+      for (int j = 0; j < NR; ++j)
+#pragma unroll
+        for (int w = 0; w < NSW; ++w) sb[j][w] = (int)__builtin_amdgcn_ubfe(sb_w[j][w], fq * 8, 8);
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -483,13 +523,40 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_tn_kernel(const GemmArgs p) 
   auto compute = [&](int buf) __attribute__((always_inline)) {
     const char* As = smem + buf * STAGE;
     const char* Bs = As + A_BYTES;
-    if constexpr (is_pair<Mma>::value) {  // MX: one scaled MFMA per 128-byte K-row
+    if constexpr (F4) {  // MXFP4: two scaled MFMAs per 128-byte K-row, 16 bytes per lane each
+      // Measured (a one-hot element per (lane group, position) against per-lane scale bytes, and
+      // tests/test_mxfp4_gpu.py single-block rows): with format 4 all 32 elements of lane group
+      // g's four registers lie under the scale byte that lane group g supplies, for both
+      // operands, and lane l's byte belongs to row l & 15. Unlike fp8 (below) the obvious layout
+      // holds: 16 contiguous bytes of a row are one block. So chunk fq is block fq and chunk
+      // 4 + fq block 4 + fq of the K-tile: the fp8 path's LDS reads, one MFMA per chunk.
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int choff = ((4 * h + fq) ^ swz) * 16;
+        i32x4 af[MR], bfr[NR];
+#pragma unroll
+        for (int i = 0; i < MR; ++i)
+          af[i] = *(const i32x4*)(As + (wm * TM + i * 16 + frow) * ROWB + choff);
+#pragma unroll
+        for (int j = 0; j < NR; ++j)
+          bfr[j] = *(const i32x4*)(Bs + (wn * TN + j * 16 + frow) * ROWB + choff);
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int i = 0; i < MR; ++i)
+#pragma unroll
+          for (int j = 0; j < NR; ++j)
+            Mma::step4s(acc[i][j], bfr[j], af[i], sb[j][h * (NSW - 1)], sa[i][h * (NSW - 1)]);
+        __builtin_amdgcn_s_setprio(0);
+      }
+    } else if constexpr (is_pair<Mma>::value) {  // MX: one scaled MFMA per 128-byte K-row
       // Chunks fq and 4 + fq ARE the instruction's K order: lane group g holds K elements
       // [16 g, 16 g + 16) in its first four registers and [64 + 16 g, 64 + 16 g + 16) in its last
       // four, and the scale of K block kb = [32 kb, 32 kb + 32) is read from lane group kb
       // (measured, tests/test_mx_scaled_gpu.py single-block rows: 32 contiguous bytes per lane
       // put each half of a lane under another block's scale). So the block-scaled flavour reads
       // the same fragments and lane (frow, fq) only supplies byte fq of its row's scale word.
+      // (fp4, format 4, measured too: there the obvious layout holds, a lane group's 16 bytes are
+      // one block under its own scale byte; see the F4 branch above.)
       const int c0 = (fq ^ swz) * 16, c1 = ((4 + fq) ^ swz) * 16;
       auto frag8 = [&](const char* r) __attribute__((always_inline)) {
         const i32x4 lo = *(const i32x4*)(r + c0), hi = *(const i32x4*)(r + c1);
@@ -505,7 +572,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_tn_kernel(const GemmArgs p) 
       for (int i = 0; i < MR; ++i)
 #pragma unroll
         for (int j = 0; j < NR; ++j) {
-          if constexpr (SC) Mma::step8s(acc[i][j], bfr[j], af[i], sb[j], sa[i]);
+          if constexpr (SC) Mma::step8s(acc[i][j], bfr[j], af[i], sb[j][0], sa[i][0]);
           else Mma::step8(acc[i][j], bfr[j], af[i]);
         }
       __builtin_amdgcn_s_setprio(0);
@@ -2158,6 +2225,27 @@ hipError_t launch_mxs_cfg(const GemmArgs& p, int tile, hipStream_t s) {
     } else {
       const int tiles = ((p.M + c.rows - 1) / c.rows) * ((p.N + c.cols - 1) / c.cols);
       hipLaunchKernelGGL((gemm_tn_kernel<MmaMXS, OUT, c.rows, c.cols, c.wm, c.wn, false>),
+                         dim3(tiles), dim3(c.wm * c.wn * 64), 0, s, p);
+      return hipGetLastError();
+    }
+  });
+}
+
+// MXFP4 with block scales: the same, for the codes mx4_offers() lists. The kernel addresses
+// operand bytes (two elements each): K and the leading dimensions are halved here.
+template <int OUT>
+hipError_t launch_mx4_cfg(const GemmArgs& p_in, int tile, hipStream_t s) {
+  GemmArgs p = p_in;
+  p.K = p_in.K / 2;
+  p.lda = p_in.lda / 2;
+  p.ldb = p_in.ldb / 2;
+  return dispatch_int<kNumTileCfgs>(tile_slot(tile), [&](auto slot) {
+    constexpr TileCfg c = kTileCfgs[decltype(slot)::value];
+    if constexpr (!mx4_offers(c.code)) {
+      return hipErrorNotSupported;
+    } else {
+      const int tiles = ((p.M + c.rows - 1) / c.rows) * ((p.N + c.cols - 1) / c.cols);
+      hipLaunchKernelGGL((gemm_tn_kernel<MmaMX4S, OUT, c.rows, c.cols, c.wm, c.wn, false>),
                          dim3(tiles), dim3(c.wm * c.wn * 64), 0, s, p);
       return hipGetLastError();
     }

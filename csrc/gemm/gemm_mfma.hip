@@ -13,7 +13,9 @@
 //  * MFMA 16x16x32 (bf16/f16), 2x 16x16x32 fp8 per 16 B, 4x 16x16x4 f32 per 16 B, or the
 //    block-scaled 16x16x128 f8f6f4 (MX-fp8) that runs at 2x the bf16 rate: with unit scales, or
 //    with real per-block E8M0 scales (GemmArgs::a_scale / b_scale, the tiled kernel's MmaMXS
-//    flavour, gemm_mxs.hip; quantiser: mx_quant.hip).
+//    flavour, gemm_mxs.hip; quantiser: mx_quant.hip). With E2M1 operands (MXFP4, MmaMX4S,
+//    gemm_mx4.hip) the same instruction takes 16 bytes = 32 elements per lane, two per K-row,
+//    at twice the MX-fp8 rate; there a lane group's 16 bytes are one block under its own scale.
 //    Any k-permutation that is identical for A and B leaves the dot product unchanged, which is
 //    what lets one 16-byte ds_read feed every instruction shape. For the 16x16x128 instruction
 //    the order used (a lane's chunks fq and 4 + fq of the 128-byte K-row) is also the
@@ -79,6 +81,40 @@ int choose_tile(int64_t M, int64_t N, int64_t K, int din) {
   return TILE_128x128;
 }
 
+// DT_FP4 operands: the block-scaled MXFP4 flavour of the tiled kernel or hipErrorInvalidValue,
+// never a launch with something substituted. (a_grp / c_grp already defaulted by gemm_launch.)
+static hipError_t gemm_launch_fp4(const GemmArgs& p, int dout, int tile, int mode, hipStream_t s) {
+  if (p.a_scale == nullptr || p.b_scale == nullptr) return hipErrorInvalidValue;
+  if (dout != DT_BF16 && dout != DT_F16 && dout != DT_F32) return hipErrorInvalidValue;
+  if (mode != GEMM_MODE_AUTO && mode != GEMM_MODE_MX) return hipErrorInvalidValue;
+  if (tile != TILE_AUTO && !mx4_offers(tile)) return hipErrorInvalidValue;
+  if (p.M < 0 || p.N < 0 || p.K <= 0 || p.K % 256 || p.lda % 2 || p.ldb % 2 || p.lda < p.K ||
+      p.ldb < p.K)
+    return hipErrorInvalidValue;
+  if (p.ksplit > 1 || p.a_table != nullptr || p.a_grp != (p.M > 0 ? p.M : 1) ||
+      p.flags != nullptr || p.ag_ctas > 0 || p.ag_mode != 0 || p.c_table != nullptr ||
+      p.tile_order != 0)
+    return hipErrorInvalidValue;
+  if (p.M == 0 || p.N == 0) return hipSuccess;
+  // the fast path's alignment, on the operands as the byte matrices the kernel reads
+  GemmArgs q = p;
+  q.K = p.K / 2;
+  q.lda = p.lda / 2;
+  q.ldb = p.ldb / 2;
+  if (p.a == nullptr || p.b == nullptr || p.c == nullptr || p.ldc < p.N ||
+      !gemm_fast_path_ok(q, DT_U8, dout))
+    return hipErrorInvalidValue;
+  // one aligned 64-bit load per row and K-tile, rows addressed by 32-bit byte offsets
+  if ((((uintptr_t)p.a_scale | (uintptr_t)p.b_scale) & 7) || p.a_scale_ld % 8 ||
+      p.b_scale_ld % 8 || p.a_scale_ld < p.K / 32 || p.b_scale_ld < p.K / 32 ||
+      (int64_t)p.M * p.a_scale_ld >= (int64_t(1) << 31) ||
+      (int64_t)p.N * p.b_scale_ld >= (int64_t(1) << 31))
+    return hipErrorInvalidValue;
+  if (tile == TILE_AUTO) tile = mxs_tile_for(choose_tile(p.M, p.N, p.K, DT_FP4));
+  if (tile < 0) return hipErrorInvalidValue;
+  return launch_fast_mx4(p, dout, tile, s);
+}
+
 hipError_t gemm_launch(const GemmArgs& p_in, int din, int dout, int tile, int mode,
                        hipStream_t s) {
   GemmArgs p = p_in;
@@ -86,6 +122,7 @@ hipError_t gemm_launch(const GemmArgs& p_in, int din, int dout, int tile, int mo
   if (p.c_grp <= 0) { p.c_grp = p.M > 0 ? p.M : 1; p.c_gstride = p.c_grp; }
   // known codes only (the retired families' codes are refused, not rerouted)
   if (tile != TILE_AUTO && tile_slot(tile) < 0) return hipErrorInvalidValue;
+  if (din == DT_FP4) return gemm_launch_fp4(p, dout, tile, mode, s);
   // MX block scales: both or neither; with them the tiled kernel's scaled flavour or a refusal,
   // never unit scales in their place
   if ((p.a_scale != nullptr) != (p.b_scale != nullptr)) return hipErrorInvalidValue;

@@ -13,6 +13,16 @@
 // 8-byte (4-byte) store per lane, the block's first lane stores the scale byte. A workgroup takes
 // 256 / (vectors per row) rows per pass (one, striding along K, for long rows) and grid-strides
 // over the rows; the grid is sized by the CU count. No LDS.
+//
+// The MXFP4 flavour (FP4 = true) is the same streaming kernel with OCP E2M1 elements: 6 in place
+// of 448 (e = ex - 3 if m <= 0.75 else ex - 2), q = e2m1_rne(clamp(x 2^-e, -6, 6)) with ties to the
+// even code, two elements per byte (element 2j in the low nibble of byte j), so a lane packs its
+// 8 (4) elements into 4 (2) bytes. One v_cvt_scalef32_pk_fp4_f32 converts two elements and takes
+// the block's scale 2^e as an operand (only its exponent field is read: the ldexp folds into
+// it, and e = -127 is the field 0). It is used because it matches the specification,
+// ddlb_amd/ops/mx.py quantize_mxfp4_reference, nibble for nibble on the GPU: the seven ties in
+// both signs, -0 and negative values that round to zero (0x8), subnormal inputs, s = 0
+// (tests/test_mxfp4_gpu.py). K % 256 == 0.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -60,7 +70,7 @@ template <> struct MxqIn<DT_F16> {
   }
 };
 
-template <int DT>
+template <int DT, bool FP4 = false>
 __global__ __launch_bounds__(kMxqThreads) void mx_quant_kernel(const MxQuantArgs a, int rows_pp) {
   using In = MxqIn<DT>;
   constexpr int EPV = In::kElems;   // elements per 16-byte vector
@@ -96,9 +106,26 @@ __global__ __launch_bounds__(kMxqThreads) void mx_quant_kernel(const MxQuantArgs
       }
       // amax = 1.f 2^(E - 127) = m' 2^(E - 126): m' <= 0.875 <=> fraction <= 0.75. A subnormal
       // amax (E = 0) clamps to -127 either way.
-      int e = (int)(m >> 23) - 135 + ((m & 0x7FFFFFu) > 0x600000u ? 1 : 0);
+      // (fp4: m' <= 0.75 <=> fraction <= 0.5, and 3 in place of 9)
+      int e = FP4 ? (int)(m >> 23) - 129 + ((m & 0x7FFFFFu) > 0x400000u ? 1 : 0)
+                  : (int)(m >> 23) - 135 + ((m & 0x7FFFFFu) > 0x600000u ? 1 : 0);
       e = e < -127 ? -127 : (e > 127 ? 127 : e);
       if (m == 0) e = 0;
+      if constexpr (FP4) {
+        const float sc = __builtin_bit_cast(float, (unsigned)(e + 127) << 23);
+        unsigned w = 0;
+        w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, f[0], f[1], sc, 0);
+        w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, f[2], f[3], sc, 1);
+        if constexpr (EPV == 8) {
+          w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, f[4], f[5], sc, 2);
+          w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, f[6], f[7], sc, 3);
+          *(unsigned*)(qr + (int64_t)c * 4) = w;
+        } else {
+          *(unsigned short*)(qr + (int64_t)c * 2) = (unsigned short)w;
+        }
+        if ((tid & (LPB - 1)) == 0) sr[c / LPB] = (uint8_t)(e + 127);
+        continue;
+      }
       unsigned out[EPV / 4];
 #pragma unroll
       for (int i = 0; i < EPV / 4; ++i) {
@@ -133,14 +160,18 @@ int mxq_cus() {
 
 }  // namespace
 
-hipError_t mx_quantize_launch(const MxQuantArgs& a, int din, hipStream_t s) {
+namespace {
+template <bool FP4>
+hipError_t mxq_launch(const MxQuantArgs& a, int din, hipStream_t s) {
   if (din != DT_F32 && din != DT_F16 && din != DT_BF16) return hipErrorInvalidValue;
-  if (a.R < 0 || a.K <= 0 || a.K % 128) return hipErrorInvalidValue;
+  // fp4: q rows are K / 2 bytes, stored 4 (2) bytes per lane
+  constexpr int KMOD = FP4 ? 256 : 128, QALIGN = FP4 ? 4 : 8;
+  if (a.R < 0 || a.K <= 0 || a.K % KMOD) return hipErrorInvalidValue;
   if (a.R == 0) return hipSuccess;
   const int esz = dtype_size(din);
-  if (a.x == nullptr || a.q == nullptr || a.s == nullptr || a.ldx < a.K || a.ldq < a.K ||
-      a.lds < a.K / 32 || ((uintptr_t)a.x & 15) || (a.ldx * esz) % 16 || ((uintptr_t)a.q & 7) ||
-      a.ldq % 8)
+  if (a.x == nullptr || a.q == nullptr || a.s == nullptr || a.ldx < a.K ||
+      a.ldq < (FP4 ? a.K / 2 : a.K) || a.lds < a.K / 32 || ((uintptr_t)a.x & 15) ||
+      (a.ldx * esz) % 16 || ((uintptr_t)a.q & (QALIGN - 1)) || a.ldq % QALIGN)
     return hipErrorInvalidValue;
   const int vpr = a.K / (16 / esz);
   const int rows_pp = vpr < kMxqThreads ? kMxqThreads / vpr : 1;
@@ -152,9 +183,17 @@ hipError_t mx_quantize_launch(const MxQuantArgs& a, int din, hipStream_t s) {
     hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kMxqThreads), 0, s, a, rows_pp);
     return hipGetLastError();
   };
-  if (din == DT_F32) return go(mx_quant_kernel<DT_F32>);
-  if (din == DT_F16) return go(mx_quant_kernel<DT_F16>);
-  return go(mx_quant_kernel<DT_BF16>);
+  if (din == DT_F32) return go(mx_quant_kernel<DT_F32, FP4>);
+  if (din == DT_F16) return go(mx_quant_kernel<DT_F16, FP4>);
+  return go(mx_quant_kernel<DT_BF16, FP4>);
+}
+}  // namespace
+
+hipError_t mx_quantize_launch(const MxQuantArgs& a, int din, hipStream_t s) {
+  return mxq_launch<false>(a, din, s);
+}
+hipError_t mxfp4_quantize_launch(const MxQuantArgs& a, int din, hipStream_t s) {
+  return mxq_launch<true>(a, din, s);
 }
 
 }  // namespace ddlb

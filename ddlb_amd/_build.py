@@ -39,6 +39,7 @@ SOURCES = [  # heaviest translation units first (the parallel build's critical p
     "gemm/gemm_f32_f32.hip",
     "gemm/gemm_mx.hip",
     "gemm/gemm_mxs.hip",
+    "gemm/gemm_mx4.hip",
     "gemm/mx_quant.hip",
     "gemm/gemm_generic.hip",
     "gemm/gemm_mfma.hip",

@@ -9,7 +9,8 @@ kernel launches (a bad launch can fault every GPU of the node).
 
 dtypes: bf16 -> bf16|f32, f16 -> f16|f32, f32 -> f32 (exact f32 MFMA), float8_e4m3fn -> bf16|f16|f32
 (``mode="mx"``: block-scaled MX-fp8 MFMA at 2x the bf16 rate; unit scales, or real per-block E8M0
-scales with ``a_scale`` / ``w_scale``, see :mod:`ddlb_amd.ops.mx`), f64 (generic kernel).
+scales with ``a_scale`` / ``w_scale``, see :mod:`ddlb_amd.ops.mx`), float4_e2m1fn_x2 -> bf16|f16|f32
+(MXFP4: E2M1 pairs, always with block scales, at 2x the MX-fp8 rate), f64 (generic kernel).
 """
 
 from __future__ import annotations
@@ -19,6 +20,7 @@ from typing import Optional
 from ddlb_amd.ops import load
 
 DT_F32, DT_F16, DT_BF16, DT_FP8, DT_F64, DT_U8 = 0, 1, 2, 3, 4, 5
+DT_FP4 = 6  # OCP E2M1, two elements per byte (torch.float4_e2m1fn_x2): gemm() with scales only
 # (codes 5, 8, 9, 13-15 belonged to the pp256 / p256 / p128 / pi256 / pi256w4 / r256 families,
 # retired in round 4: no auto path reached them and pt4 superseded them on every shape measured)
 TILES = {"auto": 0, "256x256": 1, "256x128": 2, "128x256": 3, "128x128": 4, "256x256w4": 6,
@@ -115,6 +117,58 @@ def split_k_factor(M: int, N: int, K: int, esz: int, ncu: int = 0) -> int:
 
 
 SCALED_TILES = ("256x128", "128x256", "128x128", "256x128w4")  # gemm.h mxs_offers()
+SCALED_FP4_TILES = ("256x128", "128x256", "128x128", "256x128w4")  # gemm.h mx4_offers()
+
+
+def _fp4_dtype():
+    import torch
+
+    return getattr(torch, "float4_e2m1fn_x2", None)
+
+
+def _is_fp4(t) -> bool:
+    dt = _fp4_dtype()
+    return dt is not None and getattr(t, "dtype", None) == dt
+
+
+def _check_fp4(a, w, out, a_scale, w_scale, M, tile, mode, a_grp, ksplit):
+    """Every refusal of the block-scaled fp4 GEMM, before anything is launched. ``a`` / ``w``
+    hold two E2M1 elements per byte: ``K = 2 * a.shape[1]``."""
+    import torch
+
+    if not (_is_fp4(a) and _is_fp4(w)):
+        raise TypeError(f"fp4 operands do not mix with another dtype (A {a.dtype}, W {w.dtype})")
+    if a_scale is None or w_scale is None:
+        raise ValueError("float4_e2m1fn_x2 operands need a_scale and w_scale (MXFP4 has no "
+                         "unit-scale kernel)")
+    if out.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+        raise TypeError("fp4 GEMM output must be bf16, f16 or f32")
+    if mode not in ("auto", "mx"):
+        raise ValueError(f"fp4 operands run the MX kernel (mode auto / mx), not mode={mode!r}")
+    if tile != "auto" and tile not in SCALED_FP4_TILES:
+        raise ValueError(f"the fp4 GEMM is offered for tile auto / {SCALED_FP4_TILES}, not "
+                         f"{tile!r}")
+    if a_grp not in (0, M):
+        raise ValueError("the fp4 GEMM needs plain A rows (no grouped A rows)")
+    if ksplit > 1:
+        raise ValueError("the fp4 GEMM does not combine with a K-split")
+    K = 2 * a.shape[1]
+    if K % 256:
+        raise ValueError(f"the fp4 GEMM needs K % 256 == 0 (K = {K})")
+    for name, sc, rows in (("a_scale", a_scale, a.shape[0]), ("w_scale", w_scale, w.shape[0])):
+        if not isinstance(sc, torch.Tensor) or sc.dtype != torch.uint8:
+            raise TypeError(f"{name} must be a uint8 tensor of E8M0 bytes")
+        if sc.device != a.device:
+            raise ValueError(f"{name} is on {sc.device}, the operands on {a.device}")
+        if tuple(sc.shape) != (rows, K // 32):
+            raise ValueError(f"{name} must have shape {(rows, K // 32)}, not {tuple(sc.shape)}")
+        if sc.stride(1) != 1 or sc.stride(0) % 8 or sc.stride(0) < K // 32:
+            raise ValueError(f"{name} needs unit inner stride and a row stride that is a "
+                             f"multiple of 8 (strides {tuple(sc.stride())})")
+        if sc.data_ptr() % 8:
+            raise ValueError(f"{name} must start at an 8-byte-aligned address")
+        if rows * sc.stride(0) >= 2 ** 31:
+            raise ValueError(f"{name} spans 2 GiB or more")
 
 
 def _check_scales(a, w, a_scale, w_scale, M, tile, mode, a_grp, ksplit):
@@ -168,15 +222,20 @@ def gemm(a, w, out=None, *, out_dtype=None, tile: str = "auto", mode: str = "aut
     ``[rows, K / 32]`` E8M0 bytes (value ``2^(s - 127)`` for 32 consecutive K elements of a row,
     :mod:`ddlb_amd.ops.mx`). They run the block-scaled flavour of the tiled kernel (tiles
     :data:`SCALED_TILES`, ``auto`` picks among them; plain A rows, no K-split); anything else
-    raises here, never a launch with unit scales in their place."""
+    raises here, never a launch with unit scales in their place.
+
+    ``float4_e2m1fn_x2`` operands (MXFP4, ``K = 2 * a.shape[1]``, ``K % 256 == 0``) always take
+    ``a_scale`` / ``w_scale``, in the same layout with 8-byte-aligned rows; tiles
+    :data:`SCALED_FP4_TILES`, output bf16 / f16 / f32, otherwise the rules above."""
     import torch
 
     C = load()
     scaled = a_scale is not None or w_scale is not None
+    fp4 = _is_fp4(a) or _is_fp4(w)
     if out is None:
         rows = M if M is not None else a.shape[0]
-        out = torch.empty((rows, w.shape[0]), dtype=out_dtype or default_out_dtype(a.dtype),
-                          device=a.device)
+        dflt = torch.bfloat16 if fp4 else default_out_dtype(a.dtype)
+        out = torch.empty((rows, w.shape[0]), dtype=out_dtype or dflt, device=a.device)
     M = a.shape[0] if M is None else int(M)
     N, K = w.shape
     a_need = _phys_rows(M, a_grp, a_gstride)
@@ -194,6 +253,19 @@ def gemm(a, w, out=None, *, out_dtype=None, tile: str = "auto", mode: str = "aut
     plain = (a_grp in (0, M) and c_grp in (0, M) and ACTS[act] == 0 and out.stride(0) == N
              and mode != "generic" and a.dtype != torch.float64)
     S = int(ksplit)
+    if fp4:
+        _check_fp4(a, w, out, a_scale, w_scale, M, tile, mode, a_grp, S)
+        K = 2 * K  # elements; the leading dimensions go in elements too
+        if M and N and not C.gemm_fast_path_ok(a.data_ptr(), w.data_ptr(), out.data_ptr(),
+                                               a.stride(0), w.stride(0), out.stride(0), M, N,
+                                               K // 2, DT_U8, dtype_code(out.dtype)):
+            raise ValueError("the fp4 GEMM needs the MFMA fast path: 16-byte-aligned operand "
+                             "rows, 8-byte-aligned output rows")
+        C.gemm(a.data_ptr(), w.data_ptr(), out.data_ptr(), 2 * a.stride(0), 2 * w.stride(0),
+               out.stride(0), M, N, K, DT_FP4, dtype_code(out.dtype), TILES[tile], MODES["mx"],
+               0, 0, c_grp, c_gstride, s, ACTS[act], 1, a_scale.data_ptr(), w_scale.data_ptr(),
+               a_scale.stride(0), w_scale.stride(0))
+        return out
     if scaled:
         _check_scales(a, w, a_scale, w_scale, M, tile, mode, a_grp, S)
         if M and N and not C.gemm_fast_path_ok(a.data_ptr(), w.data_ptr(), out.data_ptr(),

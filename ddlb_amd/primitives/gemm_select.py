@@ -57,7 +57,7 @@ class GemmBackend:
         return torch.matmul(a, w)
 
 
-QUANT_CHOICES = ["none", "mx"]
+QUANT_CHOICES = ["none", "mx", "mxfp4"]
 
 
 class MxQuantGemm:
@@ -65,32 +65,45 @@ class MxQuantGemm:
     pipe, as an fp8 linear layer runs it. The ``[n, k]`` weight is quantised once at set-up
     (:func:`ddlb_amd.ops.mx.quantize_mx`); every call quantises the activation and runs the
     block-scaled GEMM, both on the clock. Output in the benchmark dtype. HIP kernels only: it
-    raises at construction on a CPU device, with ``gemm=torch`` or for another dtype."""
+    raises at construction on a CPU device, with ``gemm=torch`` or for another dtype.
 
-    def __init__(self, backend: GemmBackend, k: int):
+    ``quant=mxfp4`` is the same recipe through MXFP4 (E2M1 elements, ``k % 256 == 0``):
+    :func:`ddlb_amd.ops.mx.quantize_mxfp4` and the block-scaled fp4 GEMM."""
+
+    def __init__(self, backend: GemmBackend, k: int, quant: str = "mx"):
+        if quant not in ("mx", "mxfp4"):
+            raise ValueError(f"quant={quant} is not a block-scaled format (mx, mxfp4)")
+        name = f"quant={quant}"
         if backend.dtype_name not in ("bfloat16", "float16"):
-            raise ValueError(f"quant=mx quantises bfloat16 or float16 inputs, not "
+            raise ValueError(f"{name} quantises bfloat16 or float16 inputs, not "
                              f"{backend.dtype_name}")
         if backend.device.type != "cuda":
-            raise ValueError("quant=mx needs a ROCm GPU (the quantiser and the scaled GEMM are "
+            raise ValueError(f"{name} needs a ROCm GPU (the quantiser and the scaled GEMM are "
                              "HIP kernels)")
         if backend.choice != "hip":
-            raise ValueError(f"quant=mx runs the hip GEMM, not gemm={backend.choice}")
-        if k % 128:
-            raise ValueError(f"quant=mx needs the GEMM's K ({k}) to be a multiple of 128")
+            raise ValueError(f"{name} runs the hip GEMM, not gemm={backend.choice}")
+        kmod = 256 if quant == "mxfp4" else 128
+        if k % kmod:
+            raise ValueError(f"{name} needs the GEMM's K ({k}) to be a multiple of {kmod}")
         from ddlb_amd.ops import gemm as _g
         from ddlb_amd.ops import mx as _mx
 
         self._g, self._mx = _g, _mx
+        if quant == "mxfp4":
+            self._quant, self._ref, self._dq = (_mx.quantize_mxfp4, _mx.quantize_mxfp4_reference,
+                                                _mx.dequantize_mxfp4)
+        else:
+            self._quant, self._ref, self._dq = (_mx.quantize_mx, _mx.quantize_mx_reference,
+                                                _mx.dequantize_mx)
         self.wq = self.ws = None
 
     def prepare_weight(self, b):
         """``b`` is ``[k, n]``; quantised as the ``[n, k]`` weight the kernel reads."""
-        self.wq, self.ws = self._mx.quantize_mx(b.t().contiguous())
+        self.wq, self.ws = self._quant(b.t().contiguous())
         return self.wq
 
     def __call__(self, a, out):
-        aq, a_s = self._mx.quantize_mx(a)
+        aq, a_s = self._quant(a)
         return self._g.gemm(aq, self.wq, out=out, a_scale=a_s, w_scale=self.ws)
 
     def expected(self, a, b):
@@ -98,7 +111,6 @@ class MxQuantGemm:
         is asked to compute. Against the unquantised product the format's own error (up to 1.85
         at k = 1024 with U[-1, 1) inputs) exceeds DDLB's ``atol = 1e-3 k``, so that rule would
         judge the number format and not the kernels."""
-        ref = self._mx.quantize_mx_reference
-        a_dq = self._mx.dequantize_mx(*ref(a))
-        w_dq = self._mx.dequantize_mx(*ref(b.t().contiguous()))
+        a_dq = self._dq(*self._ref(a))
+        w_dq = self._dq(*self._ref(b.t().contiguous()))
         return a_dq @ w_dq.t()

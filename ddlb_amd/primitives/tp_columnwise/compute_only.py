@@ -6,7 +6,8 @@ Added option ``gemm``: ``hip`` = our MFMA kernel (weight stored ``[n, k]``), ``t
 Added option ``quant``: ``none``, or ``mx`` = the bf16 / f16 activation is quantised to MX-fp8
 (e4m3 + one E8M0 scale per 32 K elements) inside the timed step and multiplied with the weight
 quantised at set-up by the block-scaled GEMM (:class:`MxQuantGemm`): what an fp8 linear layer
-pays. It is validated against the product of the dequantised operands.
+pays. It is validated against the product of the dequantised operands. ``mxfp4`` is the same
+through MXFP4 (E2M1 elements, the block-scaled fp4 GEMM; ``k % 256 == 0``).
 
 Unlike the reference, ``size=sharded`` is validated too (against the local rows) instead of
 being skipped (``compute_only.py:52-53``). Its TFLOPS keeps the reference's ``2*m*n*k``
@@ -29,7 +30,8 @@ class ComputeOnlyTPColumnwise(TPColumnwise):
         self.size = self.options["size"]
         self.a_in = self.A_unsharded if self.size == "unsharded" else self.A
         self.gemm = GemmBackend(self.options["gemm"], self.device, self.dtype)
-        self.mx = MxQuantGemm(self.gemm, self.k) if self.options["quant"] == "mx" else None
+        quant = self.options["quant"]
+        self.mx = MxQuantGemm(self.gemm, self.k, quant) if quant != "none" else None
         self.w = (self.mx or self.gemm).prepare_weight(self.B)
         self.out = self.gemm.alloc_out(self.a_in.shape[0], self.n)
 

@@ -5,7 +5,8 @@ so the GEMM share of the rowwise pipelines can be measured on its own. ``size=sh
 ``[m, k/d] x [k/d, n]`` (this rank's real work); ``unsharded`` runs the full ``[m, k] x [k, n]``.
 Validation compares against the matching fp32 product. ``quant=mx``: the activation is quantised
 to MX-fp8 inside the timed step and multiplied by the block-scaled GEMM, validated against the
-product of the dequantised operands (see the columnwise slot and :class:`MxQuantGemm`).
+product of the dequantised operands (see the columnwise slot and :class:`MxQuantGemm`);
+``quant=mxfp4`` does the same through MXFP4 and the block-scaled fp4 GEMM.
 """
 
 from __future__ import annotations
@@ -28,7 +29,8 @@ class ComputeOnlyTPRowwise(TPRowwise):
         else:
             self.a_in, b = self.A, self.B
         self._b_ref = b
-        self.mx = MxQuantGemm(self.gemm, b.shape[0]) if self.options["quant"] == "mx" else None
+        quant = self.options["quant"]
+        self.mx = MxQuantGemm(self.gemm, b.shape[0], quant) if quant != "none" else None
         self.w = (self.mx or self.gemm).prepare_weight(b)
         self.out = self.gemm.alloc_out(self.m, self.n)
 
