@@ -136,7 +136,8 @@ PYBIND11_MODULE(_C, m) {
         [](uintptr_t a, uintptr_t b, uintptr_t c, int64_t lda, int64_t ldb, int64_t ldc, int M,
            int N, int K, int din, int dout, int tile, int mode, int64_t a_grp, int64_t a_gstride,
            int64_t c_grp, int64_t c_gstride, uintptr_t stream, int act, int ksplit,
-           uintptr_t a_scale, uintptr_t b_scale, int64_t a_scale_ld, int64_t b_scale_ld) {
+           uintptr_t a_scale, uintptr_t b_scale, int64_t a_scale_ld, int64_t b_scale_ld,
+           uintptr_t c_scale, int64_t c_scale_ld) {
           GemmArgs g = make_args(a, b, c, lda, ldb, ldc, M, N, K, a_grp, a_gstride, c_grp,
                                  c_gstride);
           g.act = act;
@@ -145,6 +146,8 @@ PYBIND11_MODULE(_C, m) {
           g.b_scale = (const uint8_t*)b_scale;
           g.a_scale_ld = a_scale_ld;
           g.b_scale_ld = b_scale_ld;
+          g.c_scale = (uint8_t*)c_scale;
+          g.c_scale_ld = c_scale_ld;
           check(gemm_launch(g, din, dout, tile, mode, (hipStream_t)stream), "gemm_launch");
         },
         py::arg("a"), py::arg("b"), py::arg("c"), py::arg("lda"), py::arg("ldb"), py::arg("ldc"),
@@ -152,7 +155,8 @@ PYBIND11_MODULE(_C, m) {
         py::arg("tile") = 0, py::arg("mode") = 0, py::arg("a_grp") = 0, py::arg("a_gstride") = 0,
         py::arg("c_grp") = 0, py::arg("c_gstride") = 0, py::arg("stream") = 0,
         py::arg("act") = 0, py::arg("ksplit") = 1, py::arg("a_scale") = 0,
-        py::arg("b_scale") = 0, py::arg("a_scale_ld") = 0, py::arg("b_scale_ld") = 0);
+        py::arg("b_scale") = 0, py::arg("a_scale_ld") = 0, py::arg("b_scale_ld") = 0,
+        py::arg("c_scale") = 0, py::arg("c_scale_ld") = 0);
   m.def("mx_quantize",  // x[R, K] f32 / f16 / bf16 -> q[R, K] e4m3 + s[R, K / 32] E8M0 bytes
         [](uintptr_t x, uintptr_t q, uintptr_t sc, int64_t ldx, int64_t ldq, int64_t lds, int R,
            int K, int din, uintptr_t stream) {

@@ -173,6 +173,13 @@ struct GemmArgs {
   const uint8_t* a_scale = nullptr;
   const uint8_t* b_scale = nullptr;
   int64_t a_scale_ld = 0, b_scale_ld = 0;
+  // Quantised output (optional; dout = DT_FP8 / DT_FP4 and only then): the tiled kernel's
+  // epilogue quantises act(acc) by the MX rule in 32-column blocks of a C row and writes c as
+  // e4m3 bytes [M, N] (N % 128 == 0) or E2M1 nibble pairs [M, N / 2] (N % 256 == 0; ldc in
+  // ELEMENTS and even) and the blocks' E8M0 bytes here, [M, N / 32] with rows c_scale_ld BYTES
+  // apart: the layout the next GEMM reads as its A and a_scale. Plain C rows only.
+  uint8_t* c_scale = nullptr;
+  int64_t c_scale_ld = 0;
 };
 enum Act : int { ACT_NONE = 0, ACT_GELU = 1, ACT_RELU = 2, ACT_SILU = 3 };
 // In-kernel all-gather variants (GemmArgs::ag_mode bits; 0 = write-through publication, 8 loads

@@ -17,6 +17,10 @@ hipError_t launch_fast_mx(const GemmArgs& p, int dout, int tile, hipStream_t s);
 hipError_t launch_fast_mxs(const GemmArgs& p, int dout, int tile, hipStream_t s);
 // MXFP4 with block scales (DT_FP4 operands): the tiled kernel, offered tiles only
 hipError_t launch_fast_mx4(const GemmArgs& p, int dout, int tile, hipStream_t s);
+// Quantised output (GemmArgs::c_scale): MX-fp8 / MXFP4 data and block scales out of the tiled
+// kernel's epilogue; din bf16 / f16 / fp8 with scales / fp4 with scales, offered tiles only
+hipError_t launch_qout_fp8(const GemmArgs& p, int din, int tile, hipStream_t s);
+hipError_t launch_qout_fp4(const GemmArgs& p, int din, int tile, hipStream_t s);
 hipError_t launch_generic(const GemmArgs& p, int din, int dout, hipStream_t s);
 
 // Dispatch of the fast (MFMA) family by dtype pair; hipErrorInvalidValue if not provided.

@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "gemm.h"
+#include "mx_cvt.h"
 #include "tile_map.h"
 
 namespace ddlb {
@@ -673,22 +674,80 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_tn_kernel(const GemmArgs p) 
   compute(cur);
 
   // Epilogue: lane holds C[row = .. + frow][col = .. + 4*fq + r], r = 0..3.
-  constexpr int OSZ = out_size<OUT>();
+  if constexpr (OUT == DT_FP8 || OUT == DT_FP4) {
+    // Quantising epilogue (GemmArgs::c_scale): one MX block is 32 consecutive columns of a C row,
+    // i.e. fragments j = 2b, 2b + 1 of the four lanes frow + 16 g: 8 values per lane, then a max
+    // across lanes ^16 and ^32 (every lane takes part: rows are clamped and only the stores are
+    // predicated). TN = 64, so a block never leaves the wave; N is a whole number of blocks, so a
+    // block is wholly inside or outside, uniformly for its four lanes. launch_qout_cfg passes ldc
+    // in BYTES. The rule and the conversions: mx_cvt.h, shared with the streaming quantiser.
+    constexpr bool Q4 = OUT == DT_FP4;
+    static_assert(TN % 32 == 0, "a 32-column block stays within one wave");
 #pragma unroll
-  for (int i = 0; i < MR; ++i) {
-    const int64_t row = m0 + wm * TM + i * 16 + frow;
-    if (row >= p.M) continue;
-    char* crow = c_row<OSZ>(p, row);
+    for (int i = 0; i < MR; ++i) {
+      const int64_t row = m0 + wm * TM + i * 16 + frow;
+      const bool rok = row < p.M;
+      const int64_t rc = rok ? row : p.M - 1;
+      char* crow = (char*)p.c + rc * p.ldc;
+      uint8_t* srow = p.c_scale + rc * p.c_scale_ld;
 #pragma unroll
-    for (int j = 0; j < NR; ++j) {
-      const int64_t col = n0 + wn * TN + j * 16 + fq * 4;
-      if (col + 3 < p.N) {
-        Store4<OUT>::st(crow + col * OSZ, act4(acc[i][j], p.act));
-      } else {
-        const f32x4 a4 = act4(acc[i][j], p.act);
-        const float v[4] = {a4.x, a4.y, a4.z, a4.w};
-        for (int r = 0; r < 4; ++r)
-          if (col + r < p.N) Store4<OUT>::st1(crow + (col + r) * OSZ, v[r]);
+      for (int b = 0; b < NR / 2; ++b) {
+        const int64_t col = n0 + wn * TN + b * 32;  // the block's first column
+        const bool ok = rok && col < p.N;
+        const f32x4 v0 = act4(acc[i][2 * b], p.act), v1 = act4(acc[i][2 * b + 1], p.act);
+        const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+        unsigned m = 0;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+          const unsigned u = mx_abs_bits(v[r]);
+          m = u > m ? u : m;
+        }
+#pragma unroll
+        for (int d = 16; d <= 32; d *= 2) {
+          const unsigned o = (unsigned)__shfl_xor((int)m, d);
+          m = o > m ? o : m;
+        }
+        const int e = mx_scale_exp<Q4>(m);
+        if constexpr (Q4) {
+          const float sc = mx_fp4_scale(e);
+          unsigned w0 = 0, w1 = 0;
+          w0 = mx_cvt2_e2m1<0>(w0, v[0], v[1], sc);
+          w0 = mx_cvt2_e2m1<1>(w0, v[2], v[3], sc);
+          w1 = mx_cvt2_e2m1<0>(w1, v[4], v[5], sc);
+          w1 = mx_cvt2_e2m1<1>(w1, v[6], v[7], sc);
+          if (ok) {
+            *(unsigned short*)(crow + col / 2 + fq * 2) = (unsigned short)w0;
+            *(unsigned short*)(crow + col / 2 + 8 + fq * 2) = (unsigned short)w1;
+          }
+        } else {
+          const unsigned w0 = mx_cvt4_e4m3(v[0], v[1], v[2], v[3], e);
+          const unsigned w1 = mx_cvt4_e4m3(v[4], v[5], v[6], v[7], e);
+          if (ok) {
+            *(unsigned*)(crow + col + fq * 4) = w0;
+            *(unsigned*)(crow + col + 16 + fq * 4) = w1;
+          }
+        }
+        if (ok && fq == 0) srow[col / 32] = (uint8_t)(e + 127);
+      }
+    }
+  } else {
+    constexpr int OSZ = out_size<OUT>();
+#pragma unroll
+    for (int i = 0; i < MR; ++i) {
+      const int64_t row = m0 + wm * TM + i * 16 + frow;
+      if (row >= p.M) continue;
+      char* crow = c_row<OSZ>(p, row);
+#pragma unroll
+      for (int j = 0; j < NR; ++j) {
+        const int64_t col = n0 + wn * TN + j * 16 + fq * 4;
+        if (col + 3 < p.N) {
+          Store4<OUT>::st(crow + col * OSZ, act4(acc[i][j], p.act));
+        } else {
+          const f32x4 a4 = act4(acc[i][j], p.act);
+          const float v[4] = {a4.x, a4.y, a4.z, a4.w};
+          for (int r = 0; r < 4; ++r)
+            if (col + r < p.N) Store4<OUT>::st1(crow + (col + r) * OSZ, v[r]);
+        }
       }
     }
   }
@@ -2250,6 +2309,41 @@ hipError_t launch_mx4_cfg(const GemmArgs& p_in, int tile, hipStream_t s) {
       return hipGetLastError();
     }
   });
+}
+
+// Quantised output (OUT = DT_FP8 / DT_FP4, GemmArgs::c_scale): the tiled kernel with the
+// quantising epilogue, for the codes mxs_offers() lists; gemm_launch has checked the operands and
+// mapped the tile code. The kernel addresses C (and fp4 operand) BYTES: ldc of an fp4 output, and
+// K / lda / ldb of fp4 operands, are halved here.
+template <class Mma, int OUT>
+hipError_t launch_qout_cfg(const GemmArgs& p_in, int tile, hipStream_t s) {
+  static_assert(OUT == DT_FP8 || OUT == DT_FP4, "quantised outputs only");
+  GemmArgs p = p_in;
+  if constexpr (is_fp4<Mma>::value) {
+    p.K = p_in.K / 2;
+    p.lda = p_in.lda / 2;
+    p.ldb = p_in.ldb / 2;
+  }
+  if constexpr (OUT == DT_FP4) p.ldc = p_in.ldc / 2;
+  return dispatch_int<kNumTileCfgs>(tile_slot(tile), [&](auto slot) {
+    constexpr TileCfg c = kTileCfgs[decltype(slot)::value];
+    if constexpr (!mxs_offers(c.code)) {
+      return hipErrorNotSupported;
+    } else {
+      const int tiles = ((p.M + c.rows - 1) / c.rows) * ((p.N + c.cols - 1) / c.cols);
+      hipLaunchKernelGGL((gemm_tn_kernel<Mma, OUT, c.rows, c.cols, c.wm, c.wn, false>),
+                         dim3(tiles), dim3(c.wm * c.wn * 64), 0, s, p);
+      return hipGetLastError();
+    }
+  });
+}
+template <int OUT>
+hipError_t launch_qout(const GemmArgs& p, int din, bool scaled, int tile, hipStream_t s) {
+  if (din == DT_BF16) return launch_qout_cfg<MmaBF16, OUT>(p, tile, s);
+  if (din == DT_F16) return launch_qout_cfg<MmaF16, OUT>(p, tile, s);
+  if (din == DT_FP8 && scaled) return launch_qout_cfg<MmaMXS, OUT>(p, tile, s);
+  if (din == DT_FP4 && scaled) return launch_qout_cfg<MmaMX4S, OUT>(p, tile, s);
+  return hipErrorInvalidValue;
 }
 
 template <int DIN, int DOUT>

@@ -115,6 +115,63 @@ static hipError_t gemm_launch_fp4(const GemmArgs& p, int dout, int tile, int mod
   return launch_fast_mx4(p, dout, tile, s);
 }
 
+// Quantised output (dout = DT_FP8 / DT_FP4 with GemmArgs::c_scale): the tiled kernel's quantising
+// epilogue or hipErrorInvalidValue, never a launch with something substituted. (a_grp / c_grp
+// already defaulted by gemm_launch.)
+static hipError_t gemm_launch_qout(const GemmArgs& p, int din, int dout, int tile, int mode,
+                                   hipStream_t s) {
+  const bool q4 = dout == DT_FP4, in4 = din == DT_FP4;
+  if (p.c_scale == nullptr) return hipErrorInvalidValue;
+  if (din != DT_BF16 && din != DT_F16 && din != DT_FP8 && !in4) return hipErrorInvalidValue;
+  // fp8 / fp4 operands: block-scaled only (both scales); 16-bit operands carry none
+  const bool scaled = din == DT_FP8 || in4;
+  if (scaled ? (p.a_scale == nullptr || p.b_scale == nullptr)
+             : (p.a_scale != nullptr || p.b_scale != nullptr))
+    return hipErrorInvalidValue;
+  if (mode == GEMM_MODE_GENERIC || mode < GEMM_MODE_AUTO || mode > GEMM_MODE_MX ||
+      (!scaled && mode == GEMM_MODE_MX))
+    return hipErrorInvalidValue;
+  if (tile != TILE_AUTO && !mxs_offers(tile)) return hipErrorInvalidValue;
+  // whole 32-column blocks, as many as the GEMM that reads them takes per K-tile row
+  if (p.M < 0 || p.N < 0 || p.K <= 0 || p.N % (q4 ? 256 : 128)) return hipErrorInvalidValue;
+  if (p.ksplit > 1 || p.a_table != nullptr || p.a_grp != (p.M > 0 ? p.M : 1) ||
+      p.c_grp != (p.M > 0 ? p.M : 1) || p.flags != nullptr || p.ag_ctas > 0 || p.ag_mode != 0 ||
+      p.c_table != nullptr || p.tile_order != 0)
+    return hipErrorInvalidValue;
+  if (p.M == 0 || p.N == 0) return hipSuccess;
+  // the fast path's alignment, on operands and output as the byte matrices the kernel touches;
+  // output rows 16-byte aligned: what the GEMM that reads them as its A asks for
+  GemmArgs q = p;
+  if (in4) {
+    if (p.K % 256 || p.lda % 2 || p.ldb % 2) return hipErrorInvalidValue;
+    q.K = p.K / 2;
+    q.lda = p.lda / 2;
+    q.ldb = p.ldb / 2;
+  }
+  if (q4 && p.ldc % 2) return hipErrorInvalidValue;
+  q.ldc = q4 ? p.ldc / 2 : p.ldc;
+  if (p.a == nullptr || p.b == nullptr || p.c == nullptr || p.lda < p.K || p.ldb < p.K ||
+      p.ldc < p.N || q.ldc % 16 || ((uintptr_t)p.c & 15) ||
+      !gemm_fast_path_ok(q, in4 ? DT_U8 : din, DT_U8))
+    return hipErrorInvalidValue;
+  if (scaled) {  // one aligned 32-bit (fp4: 64-bit) load per row and K-tile, 32-bit row offsets
+    const int al = in4 ? 8 : 4;
+    if ((((uintptr_t)p.a_scale | (uintptr_t)p.b_scale) & (al - 1)) || p.a_scale_ld % al ||
+        p.b_scale_ld % al || p.a_scale_ld < p.K / 32 || p.b_scale_ld < p.K / 32 ||
+        (int64_t)p.M * p.a_scale_ld >= (int64_t(1) << 31) ||
+        (int64_t)p.N * p.b_scale_ld >= (int64_t(1) << 31))
+      return hipErrorInvalidValue;
+  }
+  // the output scales in the layout their reader takes (4-byte words; 8 for fp4 data)
+  const int cal = q4 ? 8 : 4;
+  if (((uintptr_t)p.c_scale & (cal - 1)) || p.c_scale_ld % cal || p.c_scale_ld < p.N / 32 ||
+      (int64_t)p.M * p.c_scale_ld >= (int64_t(1) << 31))
+    return hipErrorInvalidValue;
+  if (tile == TILE_AUTO) tile = mxs_tile_for(choose_tile(p.M, p.N, p.K, din));
+  if (tile < 0) return hipErrorInvalidValue;
+  return q4 ? launch_qout_fp4(p, din, tile, s) : launch_qout_fp8(p, din, tile, s);
+}
+
 hipError_t gemm_launch(const GemmArgs& p_in, int din, int dout, int tile, int mode,
                        hipStream_t s) {
   GemmArgs p = p_in;
@@ -122,6 +179,9 @@ hipError_t gemm_launch(const GemmArgs& p_in, int din, int dout, int tile, int mo
   if (p.c_grp <= 0) { p.c_grp = p.M > 0 ? p.M : 1; p.c_gstride = p.c_grp; }
   // known codes only (the retired families' codes are refused, not rerouted)
   if (tile != TILE_AUTO && tile_slot(tile) < 0) return hipErrorInvalidValue;
+  // quantised output: dout fp8 / fp4 and output scales go together
+  if (dout == DT_FP8 || dout == DT_FP4) return gemm_launch_qout(p, din, dout, tile, mode, s);
+  if (p.c_scale != nullptr) return hipErrorInvalidValue;
   if (din == DT_FP4) return gemm_launch_fp4(p, dout, tile, mode, s);
   // MX block scales: both or neither; with them the tiled kernel's scaled flavour or a refusal,
   // never unit scales in their place

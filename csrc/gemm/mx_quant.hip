@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "gemm.h"
+#include "mx_cvt.h"
 
 namespace ddlb {
 namespace {
@@ -104,21 +105,15 @@ __global__ __launch_bounds__(kMxqThreads) void mx_quant_kernel(const MxQuantArgs
         const unsigned o = (unsigned)__shfl_xor((int)m, d);
         m = o > m ? o : m;
       }
-      // amax = 1.f 2^(E - 127) = m' 2^(E - 126): m' <= 0.875 <=> fraction <= 0.75. A subnormal
-      // amax (E = 0) clamps to -127 either way.
-      // (fp4: m' <= 0.75 <=> fraction <= 0.5, and 3 in place of 9)
-      int e = FP4 ? (int)(m >> 23) - 129 + ((m & 0x7FFFFFu) > 0x400000u ? 1 : 0)
-                  : (int)(m >> 23) - 135 + ((m & 0x7FFFFFu) > 0x600000u ? 1 : 0);
-      e = e < -127 ? -127 : (e > 127 ? 127 : e);
-      if (m == 0) e = 0;
+      const int e = mx_scale_exp<FP4>(m);  // (mx_cvt.h: the rule, shared with the GEMM epilogue)
       if constexpr (FP4) {
-        const float sc = __builtin_bit_cast(float, (unsigned)(e + 127) << 23);
+        const float sc = mx_fp4_scale(e);
         unsigned w = 0;
-        w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, f[0], f[1], sc, 0);
-        w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, f[2], f[3], sc, 1);
+        w = mx_cvt2_e2m1<0>(w, f[0], f[1], sc);
+        w = mx_cvt2_e2m1<1>(w, f[2], f[3], sc);
         if constexpr (EPV == 8) {
-          w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, f[4], f[5], sc, 2);
-          w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, f[6], f[7], sc, 3);
+          w = mx_cvt2_e2m1<2>(w, f[4], f[5], sc);
+          w = mx_cvt2_e2m1<3>(w, f[6], f[7], sc);
           *(unsigned*)(qr + (int64_t)c * 4) = w;
         } else {
           *(unsigned short*)(qr + (int64_t)c * 2) = (unsigned short)w;
@@ -128,15 +123,8 @@ __global__ __launch_bounds__(kMxqThreads) void mx_quant_kernel(const MxQuantArgs
       }
       unsigned out[EPV / 4];
 #pragma unroll
-      for (int i = 0; i < EPV / 4; ++i) {
-        float y[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          y[j] = __builtin_amdgcn_fmed3f(__builtin_ldexpf(f[4 * i + j], -e), -448.f, 448.f);
-        int w = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0, false);
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], w, true);
-        out[i] = (unsigned)w;
-      }
+      for (int i = 0; i < EPV / 4; ++i)
+        out[i] = mx_cvt4_e4m3(f[4 * i], f[4 * i + 1], f[4 * i + 2], f[4 * i + 3], e);
       if constexpr (EPV == 8)
         *(uint2*)(qr + (int64_t)c * 8) = uint2{out[0], out[1]};
       else

@@ -37,6 +37,8 @@ SOURCES = [  # heaviest translation units first (the parallel build's critical p
     "gemm/gemm_f16_f16.hip",
     "gemm/gemm_f16_f32.hip",
     "gemm/gemm_f32_f32.hip",
+    "gemm/gemm_qout_fp8.hip",
+    "gemm/gemm_qout_fp4.hip",
     "gemm/gemm_mx.hip",
     "gemm/gemm_mxs.hip",
     "gemm/gemm_mx4.hip",
@@ -49,7 +51,7 @@ SOURCES = [  # heaviest translation units first (the parallel build's critical p
     "bindings.cpp",
 ]
 HEADERS = ["gemm/gemm.h", "gemm/gemm_kernels.h", "gemm/gemm_entry.h", "gemm/tile_map.h",
-           "runtime/kernels.h",
+           "gemm/mx_cvt.h", "runtime/kernels.h",
            "comm/comm.h", "runtime/plan.h", "runtime/plan_ir.h"]
 
 

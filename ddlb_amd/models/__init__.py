@@ -3,6 +3,8 @@
 * :mod:`ddlb_amd.models.shapes`  — TP GEMM shapes of real transformer layers (Llama 3, GPT-3,
   Qwen2, Mixtral) -> benchmark sweeps (``python -m ddlb_amd.models``).
 * :mod:`ddlb_amd.models.tp_mlp`  — sequence-parallel TP MLP block (AG+GEMM+act -> GEMM+RS).
+* :mod:`ddlb_amd.models.mx_mlp`  — one-GPU MLP on the block-scaled matrix pipe (MX-fp8 / MXFP4):
+  fc1 writes its activation quantised from the GEMM epilogue, fc2 reads it.
 """
 
 from ddlb_amd.models.shapes import MODELS, LayerGemm, ModelSpec, benchmark_configs, layer_gemms

@@ -11,6 +11,8 @@ dtypes: bf16 -> bf16|f32, f16 -> f16|f32, f32 -> f32 (exact f32 MFMA), float8_e4
 (``mode="mx"``: block-scaled MX-fp8 MFMA at 2x the bf16 rate; unit scales, or real per-block E8M0
 scales with ``a_scale`` / ``w_scale``, see :mod:`ddlb_amd.ops.mx`), float4_e2m1fn_x2 -> bf16|f16|f32
 (MXFP4: E2M1 pairs, always with block scales, at 2x the MX-fp8 rate), f64 (generic kernel).
+``out_quant="mx" | "mxfp4"``: bf16 / f16 / block-scaled fp8 / block-scaled fp4 -> MX-fp8 or MXFP4
+data and E8M0 scales per 32 output columns, quantised in the GEMM's epilogue.
 """
 
 from __future__ import annotations
@@ -207,10 +209,174 @@ def _check_scales(a, w, a_scale, w_scale, M, tile, mode, a_grp, ksplit):
             raise ValueError(f"{name} spans 2 GiB or more")
 
 
+OUT_QUANTS = ("mx", "mxfp4")
+
+
+def out_quant_dtype(out_quant: str):
+    import torch
+
+    return _fp4_dtype() if out_quant == "mxfp4" else torch.float8_e4m3fn
+
+
+def _check_out_quant(a, w, out_quant, out=None, out_scale=None, *, a_scale=None, w_scale=None,
+                     tile: str = "auto", mode: str = "auto", M: Optional[int] = None,
+                     a_grp: int = 0, c_grp: int = 0, ksplit: int = 0, out_dtype=None):
+    """Every refusal of the quantised-output GEMM (``out_quant="mx" | "mxfp4"``), on the host and
+    before anything is loaded or launched (CPU tensors pass through it). ``out`` / ``out_scale``
+    are checked when given. Returns ``(M, N, K)`` in elements."""
+    import torch
+    from types import SimpleNamespace
+
+    if out_quant not in OUT_QUANTS:
+        raise ValueError(f"out_quant must be None or one of {OUT_QUANTS}, not {out_quant!r}")
+    q4 = out_quant == "mxfp4"
+    if q4 and _fp4_dtype() is None:
+        raise TypeError("out_quant='mxfp4' needs torch.float4_e2m1fn_x2")
+    qdt = out_quant_dtype(out_quant)
+    if a.dim() != 2 or w.dim() != 2:
+        raise ValueError("native GEMM expects 2-D operands")
+    fp4 = _is_fp4(a) or _is_fp4(w)
+    M = a.shape[0] if M is None else int(M)
+    N = w.shape[0]
+    K = 2 * a.shape[1] if fp4 else a.shape[1]
+    if a.shape[1] != w.shape[1]:
+        raise ValueError(f"K mismatch: A {tuple(a.shape)} vs W {tuple(w.shape)}")
+    if not 0 <= M <= a.shape[0]:
+        raise ValueError(f"M = {M} is outside A's {a.shape[0]} rows")
+    if out_dtype is not None and out_dtype != qdt:
+        raise TypeError(f"out_quant={out_quant!r} writes {qdt}, not out_dtype={out_dtype}")
+    nmod = 256 if q4 else 128
+    if N % nmod:
+        raise ValueError(f"out_quant={out_quant!r} needs N % {nmod} == 0 (N = {N}): whole "
+                         "32-column blocks, as many as the GEMM that reads them takes per K-tile")
+    if mode == "generic":
+        raise ValueError("a quantised output comes from the tiled MFMA kernel, not mode='generic'")
+    if mode not in MODES:
+        raise ValueError(f"unknown mode {mode!r}")
+    if tile != "auto" and tile not in SCALED_TILES:
+        raise ValueError(f"a quantised output is offered for tile auto / {SCALED_TILES}, not "
+                         f"{tile!r}")
+    if int(ksplit) > 1:
+        raise ValueError("a quantised output does not combine with a K-split")
+    if a_grp not in (0, M) or c_grp not in (0, M):
+        raise ValueError("a quantised output needs plain A and C rows (no grouped rows)")
+    # the inputs: bf16, f16, block-scaled fp8, block-scaled fp4
+    if fp4:
+        _check_fp4(a, w, SimpleNamespace(dtype=torch.bfloat16), a_scale, w_scale, M, tile, mode,
+                   a_grp, int(ksplit))
+    elif a.dtype == torch.float8_e4m3fn or w.dtype == torch.float8_e4m3fn:
+        if a.dtype != w.dtype:
+            raise TypeError(f"A dtype {a.dtype} != W dtype {w.dtype}")
+        if a_scale is None or w_scale is None:
+            raise ValueError("a quantised output from fp8 operands needs a_scale and w_scale "
+                             "(there is no unit-scale kernel with this epilogue)")
+        _check_scales(a, w, a_scale, w_scale, M, tile, mode, a_grp, int(ksplit))
+    elif a.dtype in (torch.bfloat16, torch.float16):
+        if a.dtype != w.dtype:
+            raise TypeError(f"A dtype {a.dtype} != W dtype {w.dtype}")
+        if a_scale is not None or w_scale is not None:
+            raise TypeError(f"block scales need fp8 / fp4 operands, not {a.dtype}")
+        if mode == "mx":
+            raise ValueError(f"mode='mx' needs fp8 / fp4 operands, not {a.dtype}")
+    else:
+        raise TypeError(f"out_quant takes bf16, f16, scaled fp8 or scaled fp4 operands, not "
+                        f"{a.dtype}")
+    if M >= 2 ** 31 or N >= 2 ** 31 or K >= 2 ** 31:
+        raise ValueError("dimensions must fit in 32 bits")
+    ncol, sal = (N // 2 if q4 else N), (8 if q4 else 4)
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != qdt:
+            raise TypeError(f"out must be a {qdt} tensor for out_quant={out_quant!r}, not "
+                            f"{getattr(out, 'dtype', type(out))}")
+        if out.device != a.device:
+            raise ValueError(f"out is on {out.device}, the operands on {a.device}")
+        if out.dim() != 2 or out.shape[0] < M or out.shape[1] != ncol:
+            raise ValueError(f"out must have shape (>= {M}, {ncol}), not {tuple(out.shape)}")
+        if out.stride(1) != 1 or out.stride(0) < ncol or out.stride(0) % 16:
+            raise ValueError(f"out needs unit inner stride and a row stride that is a multiple "
+                             f"of 16 bytes (strides {tuple(out.stride())})")
+        if out.data_ptr() % 16:
+            raise ValueError("out must start at a 16-byte-aligned address")
+    if out_scale is not None:
+        if not isinstance(out_scale, torch.Tensor) or out_scale.dtype != torch.uint8:
+            raise TypeError("out_scale must be a uint8 tensor of E8M0 bytes")
+        if out_scale.device != a.device:
+            raise ValueError(f"out_scale is on {out_scale.device}, the operands on {a.device}")
+        if out_scale.dim() != 2 or out_scale.shape[0] < M or out_scale.shape[1] != N // 32:
+            raise ValueError(f"out_scale must have shape (>= {M}, {N // 32}), not "
+                             f"{tuple(out_scale.shape)}")
+        if (out_scale.stride(1) != 1 or out_scale.stride(0) < N // 32
+                or out_scale.stride(0) % sal):
+            raise ValueError(f"out_scale needs unit inner stride and a row stride that is a "
+                             f"multiple of {sal} (strides {tuple(out_scale.stride())})")
+        if M * out_scale.stride(0) >= 2 ** 31:
+            raise ValueError("out_scale spans 2 GiB or more")
+        if out_scale.data_ptr() % sal:
+            raise ValueError(f"out_scale must start at a {sal}-byte-aligned address")
+    if M * (N // 32) >= 2 ** 31:
+        raise ValueError("out_scale spans 2 GiB or more")
+    return M, N, K
+
+
+def _check_quant_operands(a, w):
+    if a.device.type != "cuda" or w.device.type != "cuda":
+        raise ValueError("native GEMM operands must be ROCm device tensors")
+    if a.device != w.device:
+        raise ValueError("operands on different devices")
+    if a.stride(1) != 1 or w.stride(1) != 1:
+        raise ValueError("operands must be row-major with unit inner stride")
+
+
+def _gemm_out_quant(a, w, out, out_scale, out_quant, *, out_dtype, tile, mode, M, a_grp, c_grp,
+                    stream, act, ksplit, a_scale, w_scale):
+    """The quantised-output launch: ``(q, s)`` written by the tiled kernel's epilogue. Every
+    refusal comes first, before the extension is loaded."""
+    import torch
+
+    if act not in ACTS:
+        raise ValueError(f"unknown activation {act!r}")
+    M, N, K = _check_out_quant(a, w, out_quant, out, out_scale, a_scale=a_scale, w_scale=w_scale,
+                               tile=tile, mode=mode, M=M, a_grp=a_grp, c_grp=c_grp, ksplit=ksplit,
+                               out_dtype=out_dtype)
+    C = load()
+    q4 = out_quant == "mxfp4"
+    fp4 = _is_fp4(a)
+    ncol = N // 2 if q4 else N
+    _check_quant_operands(a, w)
+    # dense rows are what the consumer asks of a / a_scale: N % 128 (256) makes a data row a
+    # multiple of 16 bytes and a scale row a multiple of 4 (8)
+    if out is None:
+        out = torch.empty((M, ncol), dtype=torch.uint8,
+                          device=a.device).view(out_quant_dtype(out_quant))
+    if out_scale is None:
+        out_scale = torch.empty((M, N // 32), dtype=torch.uint8, device=a.device)
+    kb = K // 2 if fp4 else K  # the operands as the byte / element matrices the kernel reads
+    if M and N and not C.gemm_fast_path_ok(a.data_ptr(), w.data_ptr(), out.data_ptr(),
+                                           a.stride(0), w.stride(0), out.stride(0), M, N, kb,
+                                           DT_U8 if fp4 else dtype_code(a.dtype), DT_U8):
+        raise ValueError("a quantised output needs the MFMA fast path: 16-byte-aligned operand "
+                         "rows and K a whole number of 128-byte K-tiles")
+    s = stream if stream is not None else torch.cuda.current_stream(a.device).cuda_stream
+    scaled = a_scale is not None
+    # (ksplit 1: neither a requested nor the automatic K-split engages on this path)
+    C.gemm(a.data_ptr(), w.data_ptr(), out.data_ptr(),
+           (2 if fp4 else 1) * a.stride(0), (2 if fp4 else 1) * w.stride(0),
+           (2 if q4 else 1) * out.stride(0), M, N, K,
+           DT_FP4 if fp4 else dtype_code(a.dtype), DT_FP4 if q4 else DT_FP8, TILES[tile],
+           MODES["mx"] if scaled else MODES["auto"], 0, 0, 0, 0, s, ACTS[act], 1,
+           a_scale.data_ptr() if scaled else 0, w_scale.data_ptr() if scaled else 0,
+           a_scale.stride(0) if scaled else 0, w_scale.stride(0) if scaled else 0,
+           out_scale.data_ptr(), out_scale.stride(0))
+    if stream is not None:  # the outputs stay allocated until that stream reaches them
+        out.record_stream(torch.cuda.ExternalStream(s))
+        out_scale.record_stream(torch.cuda.ExternalStream(s))
+    return out[:M], out_scale[:M]
+
+
 def gemm(a, w, out=None, *, out_dtype=None, tile: str = "auto", mode: str = "auto",
          M: Optional[int] = None, a_grp: int = 0, a_gstride: int = 0, c_grp: int = 0,
          c_gstride: int = 0, stream=None, act: str = "none", ksplit: int = 0,
-         a_scale=None, w_scale=None):
+         a_scale=None, w_scale=None, out_quant: Optional[str] = None, out_scale=None):
     """``out[:M] = act(a[:M] @ w.T)`` on the current HIP stream (grouped-row addressing and a
     fused epilogue activation — none / gelu (tanh) / relu / silu — optional). ``ksplit``: 0 =
     auto (:func:`split_k_factor` for plain-row auto-tile GEMMs with no activation and a dense
@@ -226,9 +392,25 @@ def gemm(a, w, out=None, *, out_dtype=None, tile: str = "auto", mode: str = "aut
 
     ``float4_e2m1fn_x2`` operands (MXFP4, ``K = 2 * a.shape[1]``, ``K % 256 == 0``) always take
     ``a_scale`` / ``w_scale``, in the same layout with 8-byte-aligned rows; tiles
-    :data:`SCALED_FP4_TILES`, output bf16 / f16 / f32, otherwise the rules above."""
+    :data:`SCALED_FP4_TILES`, output bf16 / f16 / f32, otherwise the rules above.
+
+    ``out_quant="mx"`` / ``"mxfp4"`` (bf16, f16, scaled fp8 or scaled fp4 operands; tiles
+    :data:`SCALED_TILES`; ``N % 128`` / ``N % 256 == 0``; plain rows, no K-split): the epilogue
+    quantises ``act(acc)`` in f32 by the rule of :mod:`ddlb_amd.ops.mx`, in blocks of 32
+    consecutive columns of a row, and ``gemm`` returns ``(q, s)``: ``float8_e4m3fn [M, N]`` or
+    ``float4_e2m1fn_x2 [M, N / 2]`` and ``uint8 [M, N / 32]``, laid out so that they go straight
+    back in as ``a`` and ``a_scale``. ``out`` / ``out_scale`` may be preallocated (16-byte-aligned
+    data rows, a scale row stride that is a multiple of 4, 8 for fp4). :func:`_check_out_quant`
+    holds every refusal."""
     import torch
 
+    if out_quant is None and out_scale is not None:
+        raise ValueError("out_scale goes with out_quant")
+    if out_quant is not None:
+        return _gemm_out_quant(a, w, out, out_scale, out_quant, out_dtype=out_dtype,
+                               tile=tile, mode=mode, M=M, a_grp=a_grp, c_grp=c_grp,
+                               stream=stream, act=act, ksplit=ksplit, a_scale=a_scale,
+                               w_scale=w_scale)
     C = load()
     scaled = a_scale is not None or w_scale is not None
     fp4 = _is_fp4(a) or _is_fp4(w)
