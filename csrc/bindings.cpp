@@ -179,6 +179,22 @@ PYBIND11_MODULE(_C, m) {
         },
         py::arg("x"), py::arg("q"), py::arg("s"), py::arg("ldx"), py::arg("ldq"),
         py::arg("lds"), py::arg("R"), py::arg("K"), py::arg("din"), py::arg("stream") = 0);
+  m.def("mx_quantize_t",  // x[R, C] -> qt[C, R] (fp4: [C, R / 2]) + st[C, R / 32], blocks down
+        // the columns of x; two: also the row-wise q[R, C] (fp4: [R, C / 2]) + s[R, C / 32]
+        [](uintptr_t x, uintptr_t qt, uintptr_t st, int64_t ldx, int64_t ldqt, int64_t ldst,
+           int R, int C, int din, bool fp4, uintptr_t stream, bool two, uintptr_t q,
+           uintptr_t sc, int64_t ldq, int64_t lds) {
+          MxQuantTArgs a;
+          a.x = (const void*)x; a.qt = (void*)qt; a.st = (uint8_t*)st;
+          a.q = (void*)q; a.s = (uint8_t*)sc;
+          a.ldx = ldx; a.ldqt = ldqt; a.ldst = ldst; a.ldq = ldq; a.lds = lds;
+          a.R = R; a.C = C;
+          check(mx_quantize_t_launch(a, din, fp4, two, (hipStream_t)stream), "mx_quantize_t");
+        },
+        py::arg("x"), py::arg("qt"), py::arg("st"), py::arg("ldx"), py::arg("ldqt"),
+        py::arg("ldst"), py::arg("R"), py::arg("C"), py::arg("din"), py::arg("fp4") = false,
+        py::arg("stream") = 0, py::arg("two") = false, py::arg("q") = 0, py::arg("s") = 0,
+        py::arg("ldq") = 0, py::arg("lds") = 0);
   m.attr("MX4_TILES") = [] {  // tile codes the block-scaled fp4 GEMM is built for
     std::vector<int> v;
     for (int i = 0; i < kNumTileCfgs; ++i)

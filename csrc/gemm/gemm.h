@@ -212,6 +212,27 @@ hipError_t mx_quantize_launch(const MxQuantArgs& a, int din, hipStream_t s);
 // (e = ex - 3 if m <= 0.75 else ex - 2), ties to the even code. K % 256 == 0.
 hipError_t mxfp4_quantize_launch(const MxQuantArgs& a, int din, hipStream_t s);
 
+// Transposing MX quantiser (csrc/gemm/mx_quant_t.hip): x[R, C] (rows ldx ELEMENTS apart) ->
+// qt[C, R] e4m3 (fp4: [C, R / 2] nibble pairs; rows ldqt BYTES apart) and st[C, R / 32] E8M0
+// bytes (rows ldst bytes apart). A block is x[32 b .. 32 b + 31, c]: the result is the row-wise
+// quantisation of x.T, byte for byte, for a GEMM that contracts over R.
+// R % 128 == 0 (fp4: 256); C * element size % 16 == 0; x and qt rows 16-byte aligned; st base
+// and ldst multiples of 4 (fp4: 8). R == 0 or C == 0 launches nothing.
+// two = true: the same pass also writes the row-wise pair q[R, C] (fp4: [R, C / 2]; rows ldq
+// bytes apart, 8-byte aligned, fp4: 4) and s[R, C / 32], as mx_quantize_launch would;
+// C % 128 == 0 (fp4: 256) then. q and s are not read otherwise.
+struct MxQuantTArgs {
+  const void* x = nullptr;
+  void* qt = nullptr;
+  uint8_t* st = nullptr;
+  void* q = nullptr;
+  uint8_t* s = nullptr;
+  int64_t ldx = 0, ldqt = 0, ldst = 0, ldq = 0, lds = 0;
+  int R = 0, C = 0;
+};
+hipError_t mx_quantize_t_launch(const MxQuantTArgs& a, int din, bool fp4, bool two,
+                                hipStream_t s);
+
 hipError_t gemm_launch(const GemmArgs& p, int din, int dout, int tile, int mode, hipStream_t s);
 bool gemm_fast_path_ok(const GemmArgs& p, int din, int dout);
 int choose_tile(int64_t M, int64_t N, int64_t K, int din);

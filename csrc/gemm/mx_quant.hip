@@ -28,48 +28,12 @@
 
 #include "gemm.h"
 #include "mx_cvt.h"
+#include "mx_quant_in.h"
 
 namespace ddlb {
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) unsigned mxq_u32x4;
 constexpr int kMxqThreads = 256;
-
-// The 16 bytes of one load as fp32 values.
-template <int DT> struct MxqIn;
-template <> struct MxqIn<DT_F32> {
-  static constexpr int kElems = 4;
-  static __device__ __forceinline__ void cvt(const mxq_u32x4 v, float* f) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const unsigned u = v[i];  // (a bit_cast of the element lvalue itself reads element 0)
-      f[i] = __builtin_bit_cast(float, u);
-    }
-  }
-};
-template <> struct MxqIn<DT_BF16> {
-  static constexpr int kElems = 8;
-  static __device__ __forceinline__ void cvt(const mxq_u32x4 v, float* f) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      f[2 * i] = __builtin_bit_cast(float, v[i] << 16);
-      f[2 * i + 1] = __builtin_bit_cast(float, v[i] & 0xFFFF0000u);
-    }
-  }
-};
-template <> struct MxqIn<DT_F16> {
-  static constexpr int kElems = 8;
-  static __device__ __forceinline__ void cvt(const mxq_u32x4 v, float* f) {
-    typedef __attribute__((ext_vector_type(2))) _Float16 h2;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const unsigned u = v[i];
-      const h2 h = __builtin_bit_cast(h2, u);
-      f[2 * i] = (float)h.x;
-      f[2 * i + 1] = (float)h.y;
-    }
-  }
-};
 
 template <int DT, bool FP4 = false>
 __global__ __launch_bounds__(kMxqThreads) void mx_quant_kernel(const MxQuantArgs a, int rows_pp) {
@@ -92,44 +56,8 @@ __global__ __launch_bounds__(kMxqThreads) void mx_quant_kernel(const MxQuantArgs
     uint8_t* sr = a.s + row * a.lds;
     for (int c = c0; c < vpr; c += kMxqThreads) {  // (lanes of a block share their trip count)
       const mxq_u32x4 v = *(const mxq_u32x4*)(xr + (int64_t)c * 16);
-      float f[EPV];
-      In::cvt(v, f);
-      unsigned m = 0;  // |x| as an integer: ordered as the floats are
-#pragma unroll
-      for (int i = 0; i < EPV; ++i) {
-        const unsigned b = __builtin_bit_cast(unsigned, f[i]) & 0x7FFFFFFFu;
-        m = b > m ? b : m;
-      }
-#pragma unroll
-      for (int d = 1; d < LPB; d *= 2) {
-        const unsigned o = (unsigned)__shfl_xor((int)m, d);
-        m = o > m ? o : m;
-      }
-      const int e = mx_scale_exp<FP4>(m);  // (mx_cvt.h: the rule, shared with the GEMM epilogue)
-      if constexpr (FP4) {
-        const float sc = mx_fp4_scale(e);
-        unsigned w = 0;
-        w = mx_cvt2_e2m1<0>(w, f[0], f[1], sc);
-        w = mx_cvt2_e2m1<1>(w, f[2], f[3], sc);
-        if constexpr (EPV == 8) {
-          w = mx_cvt2_e2m1<2>(w, f[4], f[5], sc);
-          w = mx_cvt2_e2m1<3>(w, f[6], f[7], sc);
-          *(unsigned*)(qr + (int64_t)c * 4) = w;
-        } else {
-          *(unsigned short*)(qr + (int64_t)c * 2) = (unsigned short)w;
-        }
-        if ((tid & (LPB - 1)) == 0) sr[c / LPB] = (uint8_t)(e + 127);
-        continue;
-      }
-      unsigned out[EPV / 4];
-#pragma unroll
-      for (int i = 0; i < EPV / 4; ++i)
-        out[i] = mx_cvt4_e4m3(f[4 * i], f[4 * i + 1], f[4 * i + 2], f[4 * i + 3], e);
-      if constexpr (EPV == 8)
-        *(uint2*)(qr + (int64_t)c * 8) = uint2{out[0], out[1]};
-      else
-        *(unsigned*)(qr + (int64_t)c * 4) = out[0];
-      if ((tid & (LPB - 1)) == 0) sr[c / LPB] = (uint8_t)(e + 127);
+      mxq_rowwise_vec<DT, FP4>(v, qr + (int64_t)c * (FP4 ? EPV / 2 : EPV), sr + c / LPB,
+                               (tid & (LPB - 1)) == 0);
     }
   }
 }

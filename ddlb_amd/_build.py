@@ -43,6 +43,7 @@ SOURCES = [  # heaviest translation units first (the parallel build's critical p
     "gemm/gemm_mxs.hip",
     "gemm/gemm_mx4.hip",
     "gemm/mx_quant.hip",
+    "gemm/mx_quant_t.hip",
     "gemm/gemm_generic.hip",
     "gemm/gemm_mfma.hip",
     "runtime/kernels.hip",
@@ -51,7 +52,7 @@ SOURCES = [  # heaviest translation units first (the parallel build's critical p
     "bindings.cpp",
 ]
 HEADERS = ["gemm/gemm.h", "gemm/gemm_kernels.h", "gemm/gemm_entry.h", "gemm/tile_map.h",
-           "gemm/mx_cvt.h", "runtime/kernels.h",
+           "gemm/mx_cvt.h", "gemm/mx_quant_in.h", "runtime/kernels.h",
            "comm/comm.h", "runtime/plan.h", "runtime/plan_ir.h"]
 
 

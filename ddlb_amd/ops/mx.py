@@ -248,3 +248,172 @@ def quantize_mxfp4(x, *, stream=None):
             q.record_stream(torch.cuda.ExternalStream(st))
             s.record_stream(torch.cuda.ExternalStream(st))
     return q.view(torch.float4_e2m1fn_x2), s
+
+
+# ---------------------------------------------------------------- transposed quantisation
+# A GEMM that contracts over the ROWS of ``x [R, C]`` (a linear layer's dgrad contracts over N,
+# its wgrad over M) needs the blocks down the columns of ``x`` and those blocks stored as
+# K-contiguous rows: ``qt [C, R]`` (fp4: ``[C, R / 2]``) and ``st [C, R / 32]``, the row-wise
+# quantisation of ``x.T``. It is another quantisation of the tensor, not a transpose of the
+# row-wise one: a column block and a row block hold different elements and get different scales.
+T_FMTS = ("mx", "mxfp4")
+
+
+def _t_fmt(fmt: str) -> bool:
+    if fmt not in T_FMTS:
+        raise ValueError(f"fmt must be one of {T_FMTS}, not {fmt!r}")
+    return fmt == "mxfp4"
+
+
+def quantize_mx_t_reference(x, fmt: str = "mx"):
+    """``x [R, C]`` (any float dtype, any device) -> ``(qt, st)``: the reference quantisation of
+    ``x.t().contiguous()``. ``qt`` is ``[C, R]`` float8_e4m3fn (``fmt="mxfp4"``: ``[C, R / 2]``
+    float4_e2m1fn_x2), ``st`` is ``[C, R / 32]`` uint8. The specification of
+    :func:`quantize_mx_t`."""
+    fp4 = _t_fmt(fmt)
+    if x.dim() != 2:
+        raise ValueError(f"MX quantisation expects a 2-D tensor, not {tuple(x.shape)}")
+    xt = x.t().contiguous()
+    return quantize_mxfp4_reference(xt) if fp4 else quantize_mx_reference(xt)
+
+
+def _check_quant_t(x, fmt: str, out=None, *, two_way: bool = False):
+    """Every refusal of :func:`quantize_mx_t` / :func:`quantize_mx_2way`, on the host and before
+    the extension is loaded (CPU tensors reach the device refusal). Returns ``(R, C, fp4)``."""
+    import torch
+
+    name = "quantize_mx_2way" if two_way else "quantize_mx_t"
+    fp4 = _t_fmt(fmt)
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{name} expects a tensor")
+    if x.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+        raise TypeError(f"{name} takes {IN_DTYPES}, not {x.dtype}")
+    if fp4 and not hasattr(torch, "float4_e2m1fn_x2"):
+        raise TypeError("fmt='mxfp4' needs torch.float4_e2m1fn_x2")
+    if x.dim() != 2:
+        raise ValueError(f"{name} expects a 2-D tensor, not {tuple(x.shape)}")
+    R, C = x.shape
+    mod = 256 if fp4 else 128
+    if R % mod:
+        raise ValueError(f"{name}(fmt={fmt!r}) needs R % {mod} == 0 (x is {R} x {C}): R is the K "
+                         "of the GEMM that reads the transposed result")
+    if (C * x.element_size()) % 16:
+        raise ValueError(f"{name} needs rows of whole 16-byte vectors (x is {R} x {C} {x.dtype})")
+    if two_way and C % mod:
+        raise ValueError(f"{name}(fmt={fmt!r}) needs C % {mod} == 0 as well (x is {R} x {C})")
+    if R >= 2 ** 31 or C >= 2 ** 31:
+        raise ValueError("dimensions must fit in 32 bits")
+    empty = R == 0 or C == 0  # nothing is read: torch gives such a tensor any strides
+    if not empty and (x.stride(1) != 1 or (R > 1 and x.stride(0) < C)):
+        raise ValueError(f"{name} needs row-major input with unit inner stride")
+    if not empty and (x.data_ptr() % 16 or (x.stride(0) * x.element_size()) % 16):
+        raise ValueError(f"{name} needs 16-byte-aligned rows")
+    if R * max(x.stride(0), C) * x.element_size() >= 2 ** 31:
+        raise ValueError(f"{name}: x spans 2 GiB or more")
+    ncol, sal = (R // 2 if fp4 else R), (8 if fp4 else 4)
+    if out is not None:
+        if two_way:
+            raise ValueError(f"{name} allocates its outputs")
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise TypeError("out must be a pair (qt, st)")
+        qt, st = out
+        qdt = torch.float4_e2m1fn_x2 if fp4 else torch.float8_e4m3fn
+        if not isinstance(qt, torch.Tensor) or qt.dtype != qdt:
+            raise TypeError(f"out[0] must be a {qdt} tensor for fmt={fmt!r}, not "
+                            f"{getattr(qt, 'dtype', type(qt))}")
+        if not isinstance(st, torch.Tensor) or st.dtype != torch.uint8:
+            raise TypeError("out[1] must be a uint8 tensor of E8M0 bytes")
+        if qt.device != x.device or st.device != x.device:
+            raise ValueError(f"out is on {qt.device} / {st.device}, x on {x.device}")
+        if tuple(qt.shape) != (C, ncol):
+            raise ValueError(f"out[0] must have shape {(C, ncol)}, not {tuple(qt.shape)}")
+        if tuple(st.shape) != (C, R // BLOCK):
+            raise ValueError(f"out[1] must have shape {(C, R // BLOCK)}, not {tuple(st.shape)}")
+        if qt.stride(1) != 1 or qt.stride(0) < ncol or qt.stride(0) % 16:
+            raise ValueError(f"out[0] needs unit inner stride and a row stride that is a "
+                             f"multiple of 16 bytes (strides {tuple(qt.stride())})")
+        if qt.data_ptr() % 16:
+            raise ValueError("out[0] must start at a 16-byte-aligned address")
+        if st.stride(1) != 1 or st.stride(0) < R // BLOCK or st.stride(0) % sal:
+            raise ValueError(f"out[1] needs unit inner stride and a row stride that is a "
+                             f"multiple of {sal} (strides {tuple(st.stride())})")
+        if st.data_ptr() % sal:
+            raise ValueError(f"out[1] must start at a {sal}-byte-aligned address")
+        if C * qt.stride(0) >= 2 ** 31 or C * st.stride(0) >= 2 ** 31:
+            raise ValueError("out spans 2 GiB or more")
+    if C * ncol >= 2 ** 31:
+        raise ValueError(f"{name}: the quantised tensor spans 2 GiB or more")
+    if x.device.type != "cuda":  # last, so that CPU tensors reach every refusal above
+        raise ValueError(f"{name} needs a ROCm device tensor (quantize_mx_t_reference runs "
+                         "anywhere)")
+    return R, C, fp4
+
+
+def _launch_quant_t(x, R, C, fp4, qt, st, q, s, stream):
+    import torch
+
+    from ddlb_amd.ops import load
+    from ddlb_amd.ops.gemm import dtype_code
+
+    C_ = load()
+    if R == 0 or C == 0:
+        return
+    strm = stream if stream is not None else torch.cuda.current_stream(x.device).cuda_stream
+    two = q is not None
+    with torch.cuda.device(x.device):
+        C_.mx_quantize_t(x.data_ptr(), qt.data_ptr(), st.data_ptr(), max(x.stride(0), C),
+                         qt.stride(0), st.stride(0), R, C, dtype_code(x.dtype), fp4, strm, two,
+                         q.data_ptr() if two else 0, s.data_ptr() if two else 0,
+                         q.stride(0) if two else 0, s.stride(0) if two else 0)
+    if stream is not None:  # the outputs stay allocated until that stream reaches them
+        for t in (qt, st, q, s):
+            if t is not None:
+                t.record_stream(torch.cuda.ExternalStream(strm))
+
+
+def _alloc_quant(rows, cols, fp4, device):
+    """Dense quantised data (as bytes) and scales of a ``[rows, cols]``-element tensor."""
+    import torch
+
+    q = torch.empty((rows, cols // 2 if fp4 else cols), dtype=torch.uint8, device=device)
+    return q, torch.empty((rows, cols // BLOCK), dtype=torch.uint8, device=device)
+
+
+def quantize_mx_t(x, *, fmt: str = "mx", out=None, stream=None):
+    """The HIP transposing quantiser (``csrc/gemm/mx_quant_t.hip``): ``x [R, C]`` bf16 / f16 /
+    f32 on a ROCm device -> ``(qt, st)`` as :func:`quantize_mx_t_reference` computes them, byte
+    for byte, in one pass over ``x`` on ``stream`` (default: the current one). ``R % 128 == 0``
+    (``fmt="mxfp4"``: 256): ``R`` is the K of the GEMM that takes ``qt`` / ``st`` as ``a`` /
+    ``a_scale`` or ``w`` / ``w_scale``. ``C`` needs whole 16-byte vectors and nothing more.
+
+    ``out = (qt, st)`` may be preallocated, for instance views into a buffer saved for a backward
+    pass: ``qt`` ``[C, R]`` float8_e4m3fn (fp4: ``[C, R / 2]`` float4_e2m1fn_x2) with a 16-byte
+    aligned base and a row stride that is a multiple of 16; ``st`` ``[C, R / 32]`` uint8 with base
+    and row stride multiples of 4 (fp4: 8). Every refusal is raised here, before the launch."""
+    import torch
+
+    R, C, fp4 = _check_quant_t(x, fmt, out)
+    if out is None:
+        qt, st = _alloc_quant(C, R, fp4, x.device)
+        if fp4:
+            qt = qt.view(torch.float4_e2m1fn_x2)
+        else:
+            qt = qt.view(torch.float8_e4m3fn)
+    else:
+        qt, st = out
+    _launch_quant_t(x, R, C, fp4, qt, st, None, None, stream)
+    return qt, st
+
+
+def quantize_mx_2way(x, *, fmt: str = "mx", stream=None):
+    """Both quantisations of ``x [R, C]`` in one launch that reads ``x`` once: ``(q, s, qt, st)``
+    with ``q, s`` byte-identical to :func:`quantize_mx` (:func:`quantize_mxfp4`) and ``qt, st`` to
+    :func:`quantize_mx_t`. ``R`` and ``C`` are both multiples of 128 (``fmt="mxfp4"``: 256)."""
+    import torch
+
+    R, C, fp4 = _check_quant_t(x, fmt, two_way=True)
+    qdt = torch.float4_e2m1fn_x2 if fp4 else torch.float8_e4m3fn
+    q, s = _alloc_quant(R, C, fp4, x.device)
+    qt, st = _alloc_quant(C, R, fp4, x.device)
+    _launch_quant_t(x, R, C, fp4, qt, st, q, s, stream)
+    return q.view(qdt), s, qt.view(qdt), st
