@@ -6,6 +6,9 @@ import torch
 from _exact import (FP8, POISON, SENTINEL, dequant64, exact, exact64, exact_scaled,
                     extreme_scales, ints, padded, pow2_f64, sentinel_out, untouched)
 
+from _exact_plan import (assert_exact, block_layout, gather, ksplit_operands, ksplit_specs,
+                         only_written, padded_ld, scatter)
+
 import pytest
 
 
@@ -134,3 +137,97 @@ def test_untouched_sees_a_planted_write():
     buf[2, 1] = 2.0
     with pytest.raises(AssertionError):
         untouched(buf, 8, 4, rows=rows)
+
+
+# ------------------------------------------------------------------ tests/_exact_plan.py
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32, FP8])
+@pytest.mark.parametrize("M,shard_rows,nblocks", [(1024, 256, 4), (768, 256, 4), (960, 192, 5),
+                                                  (1000, 250, 4), (1000, 256, 4), (64, 64, 1)])
+def test_block_table_gather_inverts_scatter(dtype, M, shard_rows, nblocks):
+    """The table builder followed by the gather is the identity; the blocks come in a permuted
+    order over both buffers, and every row that is no block row holds poison, as does the
+    padding of every row and the unused tail of a part-used block."""
+    K = 128
+    a = ints((M, K), dtype, _gen(6))
+    lay = block_layout(nblocks, shard_rows)
+    ld = padded_ld(K, dtype)
+    assert ld > K and (ld * a.element_size()) % 16 == 0
+    bufs = scatter(a, lay, ld)
+    assert torch.equal(gather(bufs, lay, M, K).float(), a.float())
+    assert len(set(lay.where)) == nblocks
+    if nblocks > 1:
+        assert {b for b, _ in lay.where} == {0, 1}
+        order = sorted(range(nblocks), key=lambda b: lay.where[b])
+        assert order != list(range(nblocks))
+    live = [torch.zeros((r, ld), dtype=torch.bool) for r in lay.buf_rows]
+    for b, (buf, row0) in enumerate(lay.where):
+        n = max(0, min(M, (b + 1) * shard_rows) - b * shard_rows)
+        live[buf][row0:row0 + n, :K] = True
+        # poison really lies in front of and behind every block
+        assert bool((bufs[buf][row0 - lay.gap:row0].float() == POISON).all())
+        end = row0 + shard_rows
+        assert bool((bufs[buf][end:end + lay.gap].float() == POISON).all())
+        assert end + lay.gap <= lay.buf_rows[buf]
+    for buf in (0, 1):
+        assert bool((bufs[buf].float()[~live[buf]] == POISON).all())
+        assert int(live[buf].sum()) == int((bufs[buf].float()[live[buf]] != POISON).sum())
+
+
+def test_only_written_sees_a_stray_element_and_a_missing_region():
+    def outputs():
+        bufs = {"c": torch.full((12, 10), SENTINEL, dtype=torch.bfloat16),
+                "slot": torch.full((7, 6), SENTINEL, dtype=torch.float32)}
+        bufs["c"][2:6, :8] = 1.0
+        bufs["c"][6:10, :8] = 2.0
+        bufs["slot"][torch.tensor([0, 1, 3]), :4] = 3.0
+        return bufs
+
+    regions = [("c", slice(2, 6), 8), ("c", slice(6, 10), 8), ("slot", torch.tensor([0, 1, 3]), 4)]
+    only_written(outputs(), regions)
+    for name, r, c in (("c", 0, 0), ("c", 1, 7), ("c", 5, 8), ("c", 10, 0), ("c", 11, 9),
+                       ("slot", 2, 0), ("slot", 0, 4), ("slot", 6, 5)):
+        bufs = outputs()
+        bufs[name][r, c] = 1.0                                      # a single stray element
+        with pytest.raises(AssertionError, match=f"{name}: 1"):
+            only_written(bufs, regions)
+    for skip in range(len(regions)):                                # a single missing region
+        with pytest.raises(AssertionError):
+            only_written(outputs(), regions[:skip] + regions[skip + 1:])
+    with pytest.raises(AssertionError, match="c: 64, slot: 12"):
+        only_written(outputs(), [])
+
+
+def test_assert_exact():
+    assert_exact(1024)
+    assert_exact((2 ** 24 - 1) // 9)
+    with pytest.raises(AssertionError):
+        assert_exact(2 ** 24 // 9 + 1)
+
+
+@pytest.mark.parametrize("M", [256, 512])
+def test_ksplit_specifications_differ(M):
+    """The two specifications of the public K-split (``ksplit_specs``: f32 partials rounded once;
+    output-dtype partials summed and rounded again) on the operands the GPU test uses, N = 256,
+    K = 1024. bf16 holds the integers up to 256: about 4.6 % of the products are larger, so the
+    single rounding is exercised, and with S = 2 (slice sums of standard deviation 90, 0.45 %
+    beyond 256) the specifications differ in hundreds of elements: 226 at M = 256, 422 at
+    M = 512. With S = 4 a slice sum has standard deviation 64 and passes 256 with probability
+    6e-5, so only a handful of partials are rounded at all (3 and 13 elements differ: no seed
+    reaches 100 there); f16 holds every integer up to 2048 and the products stay below 600, so
+    in f16 the specifications coincide."""
+    N, K = 256, 1024
+    a, w = ksplit_operands(M, N, K, torch.bfloat16)
+    f32 = exact(a, w, torch.float32)
+    assert float(((f32.abs() > 256).float().mean())) > 0.04
+    assert float(f32.abs().max()) < 2048
+    once, twice = ksplit_specs(a, w, 2, torch.bfloat16)
+    assert int((once != twice).sum()) > 100
+    once4, twice4 = ksplit_specs(a, w, 4, torch.bfloat16)
+    assert torch.equal(once4, once) and int((once4 != twice4).sum()) > 0
+    a16, w16 = ksplit_operands(M, N, K, torch.float16)
+    assert torch.equal(a16.float(), a.float())
+    for S in (2, 4):
+        o16, t16 = ksplit_specs(a16, w16, S, torch.float16)
+        assert torch.equal(o16, t16) and torch.equal(o16.float(), f32)
+        o32, t32 = ksplit_specs(a16.float(), w16.float(), S, torch.float32)
+        assert torch.equal(o32, t32) and torch.equal(o32, f32)
