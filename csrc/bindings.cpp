@@ -123,6 +123,30 @@ GemmArgs make_args(uintptr_t a, uintptr_t b, uintptr_t c, int64_t lda, int64_t l
   return g;
 }
 
+// The two row-wise MX quantiser bindings: one signature, one argument block, two launchers.
+void def_row_quantizer(py::module_& m, const char* name,
+                       hipError_t (*launch)(const MxQuantArgs&, int, hipStream_t)) {
+  m.def(name,
+        [name, launch](uintptr_t x, uintptr_t q, uintptr_t sc, int64_t ldx, int64_t ldq,
+                       int64_t lds, int R, int K, int din, uintptr_t stream) {
+          MxQuantArgs a;
+          a.x = (const void*)x; a.q = (void*)q; a.s = (uint8_t*)sc;
+          a.ldx = ldx; a.ldq = ldq; a.lds = lds;
+          a.R = R; a.K = K;
+          check(launch(a, din, (hipStream_t)stream), name);
+        },
+        py::arg("x"), py::arg("q"), py::arg("s"), py::arg("ldx"), py::arg("ldq"),
+        py::arg("lds"), py::arg("R"), py::arg("K"), py::arg("din"), py::arg("stream") = 0);
+}
+
+// Tile codes a flavour of the tiled kernel is built for (gemm.h mxs_offers / mx4_offers).
+std::vector<int> offered_tiles(bool (*offers)(int)) {
+  std::vector<int> v;
+  for (int i = 0; i < kNumTileCfgs; ++i)
+    if (offers(kTileCfgs[i].code)) v.push_back(kTileCfgs[i].code);
+  return v;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_C, m) {
@@ -157,28 +181,10 @@ PYBIND11_MODULE(_C, m) {
         py::arg("act") = 0, py::arg("ksplit") = 1, py::arg("a_scale") = 0,
         py::arg("b_scale") = 0, py::arg("a_scale_ld") = 0, py::arg("b_scale_ld") = 0,
         py::arg("c_scale") = 0, py::arg("c_scale_ld") = 0);
-  m.def("mx_quantize",  // x[R, K] f32 / f16 / bf16 -> q[R, K] e4m3 + s[R, K / 32] E8M0 bytes
-        [](uintptr_t x, uintptr_t q, uintptr_t sc, int64_t ldx, int64_t ldq, int64_t lds, int R,
-           int K, int din, uintptr_t stream) {
-          MxQuantArgs a;
-          a.x = (const void*)x; a.q = (void*)q; a.s = (uint8_t*)sc;
-          a.ldx = ldx; a.ldq = ldq; a.lds = lds;
-          a.R = R; a.K = K;
-          check(mx_quantize_launch(a, din, (hipStream_t)stream), "mx_quantize");
-        },
-        py::arg("x"), py::arg("q"), py::arg("s"), py::arg("ldx"), py::arg("ldq"),
-        py::arg("lds"), py::arg("R"), py::arg("K"), py::arg("din"), py::arg("stream") = 0);
-  m.def("mxfp4_quantize",  // the same -> q[R, K / 2] E2M1 nibble pairs (ldq in bytes) + s
-        [](uintptr_t x, uintptr_t q, uintptr_t sc, int64_t ldx, int64_t ldq, int64_t lds, int R,
-           int K, int din, uintptr_t stream) {
-          MxQuantArgs a;
-          a.x = (const void*)x; a.q = (void*)q; a.s = (uint8_t*)sc;
-          a.ldx = ldx; a.ldq = ldq; a.lds = lds;
-          a.R = R; a.K = K;
-          check(mxfp4_quantize_launch(a, din, (hipStream_t)stream), "mxfp4_quantize");
-        },
-        py::arg("x"), py::arg("q"), py::arg("s"), py::arg("ldx"), py::arg("ldq"),
-        py::arg("lds"), py::arg("R"), py::arg("K"), py::arg("din"), py::arg("stream") = 0);
+  // x[R, K] f32 / f16 / bf16 -> q[R, K] e4m3 + s[R, K / 32] E8M0 bytes; mxfp4_quantize: the same
+  // -> q[R, K / 2] E2M1 nibble pairs (ldq in bytes) + s
+  def_row_quantizer(m, "mx_quantize", mx_quantize_launch);
+  def_row_quantizer(m, "mxfp4_quantize", mxfp4_quantize_launch);
   m.def("mx_quantize_t",  // x[R, C] -> qt[C, R] (fp4: [C, R / 2]) + st[C, R / 32], blocks down
         // the columns of x; two: also the row-wise q[R, C] (fp4: [R, C / 2]) + s[R, C / 32]
         [](uintptr_t x, uintptr_t qt, uintptr_t st, int64_t ldx, int64_t ldqt, int64_t ldst,
@@ -195,18 +201,8 @@ PYBIND11_MODULE(_C, m) {
         py::arg("ldst"), py::arg("R"), py::arg("C"), py::arg("din"), py::arg("fp4") = false,
         py::arg("stream") = 0, py::arg("two") = false, py::arg("q") = 0, py::arg("s") = 0,
         py::arg("ldq") = 0, py::arg("lds") = 0);
-  m.attr("MX4_TILES") = [] {  // tile codes the block-scaled fp4 GEMM is built for
-    std::vector<int> v;
-    for (int i = 0; i < kNumTileCfgs; ++i)
-      if (mx4_offers(kTileCfgs[i].code)) v.push_back(kTileCfgs[i].code);
-    return v;
-  }();
-  m.attr("MXS_TILES") = [] {  // tile codes the block-scaled GEMM is built for
-    std::vector<int> v;
-    for (int i = 0; i < kNumTileCfgs; ++i)
-      if (mxs_offers(kTileCfgs[i].code)) v.push_back(kTileCfgs[i].code);
-    return v;
-  }();
+  m.attr("MX4_TILES") = offered_tiles(mx4_offers);  // the block-scaled fp4 GEMM is built for
+  m.attr("MXS_TILES") = offered_tiles(mxs_offers);  // the block-scaled fp8 GEMM is built for
   m.def("gemm_fast_path_ok",
         [](uintptr_t a, uintptr_t b, uintptr_t c, int64_t lda, int64_t ldb, int64_t ldc, int M,
            int N, int K, int din, int dout) {

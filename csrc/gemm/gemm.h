@@ -88,6 +88,16 @@ constexpr int mxs_tile_for(int tile) {
 // 140 bytes per lane; TILE_256x256_W4: 228; docs/ARCHITECTURE.md has the register table).
 constexpr bool mx4_offers(int tile) { return mxs_offers(tile); }
 
+// (launch_tiled takes the DMA interleave from kTileCfgs for every flavour: the block-scaled and
+// quantising ones are built without it, so no code they offer may carry it)
+constexpr bool offered_tiles_not_interleaved() {
+  for (int i = 0; i < kNumTileCfgs; ++i)
+    if (kTileCfgs[i].ilv && (mxs_offers(kTileCfgs[i].code) || mx4_offers(kTileCfgs[i].code)))
+      return false;
+  return true;
+}
+static_assert(offered_tiles_not_interleaved(), "scaled flavours: plain tiled codes only");
+
 constexpr bool tile_cfgs_distinct() {
   for (int i = 0; i < kNumTileCfgs; ++i)
     for (int j = i + 1; j < kNumTileCfgs; ++j)
@@ -181,6 +191,14 @@ struct GemmArgs {
   uint8_t* c_scale = nullptr;
   int64_t c_scale_ld = 0;
 };
+// The byte view of a launch whose operands and / or output are fp4: the kernels address bytes (two
+// E2M1 elements each), so K, lda and ldb of fp4 operands and ldc of an fp4 output are halved.
+// GemmArgs stay in ELEMENTS up to the launch entries (gemm_entry.h); the view is formed inside.
+constexpr GemmArgs fp4_byte_view(GemmArgs p, bool fp4_in, bool fp4_out) {
+  if (fp4_in) { p.K /= 2; p.lda /= 2; p.ldb /= 2; }
+  if (fp4_out) p.ldc /= 2;
+  return p;
+}
 enum Act : int { ACT_NONE = 0, ACT_GELU = 1, ACT_RELU = 2, ACT_SILU = 3 };
 // In-kernel all-gather variants (GemmArgs::ag_mode bits; 0 = write-through publication, 8 loads
 // in flight per lane, system-scope acquire in the GEMM gate; the plan builders pick the default,

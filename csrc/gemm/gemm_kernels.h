@@ -679,7 +679,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_tn_kernel(const GemmArgs p) 
     // i.e. fragments j = 2b, 2b + 1 of the four lanes frow + 16 g: 8 values per lane, then a max
     // across lanes ^16 and ^32 (every lane takes part: rows are clamped and only the stores are
     // predicated). TN = 64, so a block never leaves the wave; N is a whole number of blocks, so a
-    // block is wholly inside or outside, uniformly for its four lanes. launch_qout_cfg passes ldc
+    // block is wholly inside or outside, uniformly for its four lanes. launch_tiled passes ldc
     // in BYTES. The rule and the conversions: mx_cvt.h, shared with the streaming quantiser.
     constexpr bool Q4 = OUT == DT_FP4;
     static_assert(TN % 32 == 0, "a 32-column block stays within one wave");
@@ -2099,19 +2099,43 @@ hipError_t dispatch_int(int v, F&& f) {
   }
 }
 
+// f(std::integral_constant<int, dout>{}) for the three outputs the MX entries are built for.
+template <class F>
+hipError_t dispatch_out(int dout, F&& f) {
+  if (dout == DT_BF16) return f(std::integral_constant<int, DT_BF16>{});
+  if (dout == DT_F16) return f(std::integral_constant<int, DT_F16>{});
+  if (dout == DT_F32) return f(std::integral_constant<int, DT_F32>{});
+  return hipErrorInvalidValue;
+}
+
+constexpr bool offers_every_tile(int) { return true; }
+
 // The tiled kernel of a tile code (gemm.h kTileCfgs: for the ping-pong codes the interleaved
-// 256x256 one, which takes what they do not); the MX kernels are never interleaved.
+// 256x256 one, which takes what they do not; the MX kernels are never interleaved, and no code
+// that mxs_offers() / mx4_offers() list is: gemm.h). The one launch site of gemm_tn_kernel:
+// Offers is every code, or the codes a block-scaled / quantising flavour is built for; a code it
+// does not list answers hipErrorNotSupported and instantiates nothing. fp4 operands and an fp4
+// output are addressed in bytes: GemmArgs arrive in elements, the byte view is formed here.
 // hipErrorInvalidValue for a code without a kernel (5, 8, 9, 13-15: retired kernel families).
-template <class Mma, int OUT>
-hipError_t launch_tiled(const GemmArgs& p, int tile, hipStream_t s) {
-  return dispatch_int<kNumTileCfgs>(tile_slot(tile), [&](auto slot) {
-    constexpr TileCfg c = kTileCfgs[decltype(slot)::value];
-    constexpr bool ILV = c.ilv && !is_pair<Mma>::value;
-    const int tiles = ((p.M + c.rows - 1) / c.rows) * ((p.N + c.cols - 1) / c.cols);
-    hipLaunchKernelGGL((gemm_tn_kernel<Mma, OUT, c.rows, c.cols, c.wm, c.wn, ILV>), dim3(tiles),
-                       dim3(c.wm * c.wn * 64), 0, s, p);
-    return hipGetLastError();
-  });
+template <class Mma, int OUT, bool (*Offers)(int) = offers_every_tile>
+hipError_t launch_tiled(const GemmArgs& p_in, int tile, hipStream_t s) {
+  constexpr bool in4 = is_fp4<Mma>::value, out4 = OUT == DT_FP4;
+  auto launch = [&](const GemmArgs& p) {
+    return dispatch_int<kNumTileCfgs>(tile_slot(tile), [&](auto slot) {
+      constexpr TileCfg c = kTileCfgs[decltype(slot)::value];
+      if constexpr (!Offers(c.code)) {
+        return hipErrorNotSupported;
+      } else {
+        constexpr bool ILV = c.ilv && !is_pair<Mma>::value;
+        const int tiles = ((p.M + c.rows - 1) / c.rows) * ((p.N + c.cols - 1) / c.cols);
+        hipLaunchKernelGGL((gemm_tn_kernel<Mma, OUT, c.rows, c.cols, c.wm, c.wn, ILV>),
+                           dim3(tiles), dim3(c.wm * c.wn * 64), 0, s, p);
+        return hipGetLastError();
+      }
+    });
+  };
+  if constexpr (in4 || out4) return launch(fp4_byte_view(p_in, in4, out4));
+  else return launch(p_in);
 }
 
 int num_cus() {
@@ -2273,76 +2297,16 @@ hipError_t launch_mx_cfg(const GemmArgs& p, int tile, hipStream_t s) {
   return launch_tiled<MmaMX, OUT>(p, tile, s);
 }
 
-// MX-fp8 with block scales: the tiled kernel, for the codes mxs_offers() lists (gemm.h);
-// gemm_launch has checked the operands and mapped the tile code (mxs_tile_for).
-template <int OUT>
-hipError_t launch_mxs_cfg(const GemmArgs& p, int tile, hipStream_t s) {
-  return dispatch_int<kNumTileCfgs>(tile_slot(tile), [&](auto slot) {
-    constexpr TileCfg c = kTileCfgs[decltype(slot)::value];
-    if constexpr (!mxs_offers(c.code)) {
-      return hipErrorNotSupported;
-    } else {
-      const int tiles = ((p.M + c.rows - 1) / c.rows) * ((p.N + c.cols - 1) / c.cols);
-      hipLaunchKernelGGL((gemm_tn_kernel<MmaMXS, OUT, c.rows, c.cols, c.wm, c.wn, false>),
-                         dim3(tiles), dim3(c.wm * c.wn * 64), 0, s, p);
-      return hipGetLastError();
-    }
-  });
-}
-
-// MXFP4 with block scales: the same, for the codes mx4_offers() lists. The kernel addresses
-// operand bytes (two elements each): K and the leading dimensions are halved here.
-template <int OUT>
-hipError_t launch_mx4_cfg(const GemmArgs& p_in, int tile, hipStream_t s) {
-  GemmArgs p = p_in;
-  p.K = p_in.K / 2;
-  p.lda = p_in.lda / 2;
-  p.ldb = p_in.ldb / 2;
-  return dispatch_int<kNumTileCfgs>(tile_slot(tile), [&](auto slot) {
-    constexpr TileCfg c = kTileCfgs[decltype(slot)::value];
-    if constexpr (!mx4_offers(c.code)) {
-      return hipErrorNotSupported;
-    } else {
-      const int tiles = ((p.M + c.rows - 1) / c.rows) * ((p.N + c.cols - 1) / c.cols);
-      hipLaunchKernelGGL((gemm_tn_kernel<MmaMX4S, OUT, c.rows, c.cols, c.wm, c.wn, false>),
-                         dim3(tiles), dim3(c.wm * c.wn * 64), 0, s, p);
-      return hipGetLastError();
-    }
-  });
-}
-
 // Quantised output (OUT = DT_FP8 / DT_FP4, GemmArgs::c_scale): the tiled kernel with the
 // quantising epilogue, for the codes mxs_offers() lists; gemm_launch has checked the operands and
-// mapped the tile code. The kernel addresses C (and fp4 operand) BYTES: ldc of an fp4 output, and
-// K / lda / ldb of fp4 operands, are halved here.
-template <class Mma, int OUT>
-hipError_t launch_qout_cfg(const GemmArgs& p_in, int tile, hipStream_t s) {
-  static_assert(OUT == DT_FP8 || OUT == DT_FP4, "quantised outputs only");
-  GemmArgs p = p_in;
-  if constexpr (is_fp4<Mma>::value) {
-    p.K = p_in.K / 2;
-    p.lda = p_in.lda / 2;
-    p.ldb = p_in.ldb / 2;
-  }
-  if constexpr (OUT == DT_FP4) p.ldc = p_in.ldc / 2;
-  return dispatch_int<kNumTileCfgs>(tile_slot(tile), [&](auto slot) {
-    constexpr TileCfg c = kTileCfgs[decltype(slot)::value];
-    if constexpr (!mxs_offers(c.code)) {
-      return hipErrorNotSupported;
-    } else {
-      const int tiles = ((p.M + c.rows - 1) / c.rows) * ((p.N + c.cols - 1) / c.cols);
-      hipLaunchKernelGGL((gemm_tn_kernel<Mma, OUT, c.rows, c.cols, c.wm, c.wn, false>),
-                         dim3(tiles), dim3(c.wm * c.wn * 64), 0, s, p);
-      return hipGetLastError();
-    }
-  });
-}
+// mapped the tile code (mxs_tile_for).
 template <int OUT>
 hipError_t launch_qout(const GemmArgs& p, int din, bool scaled, int tile, hipStream_t s) {
-  if (din == DT_BF16) return launch_qout_cfg<MmaBF16, OUT>(p, tile, s);
-  if (din == DT_F16) return launch_qout_cfg<MmaF16, OUT>(p, tile, s);
-  if (din == DT_FP8 && scaled) return launch_qout_cfg<MmaMXS, OUT>(p, tile, s);
-  if (din == DT_FP4 && scaled) return launch_qout_cfg<MmaMX4S, OUT>(p, tile, s);
+  static_assert(OUT == DT_FP8 || OUT == DT_FP4, "quantised outputs only");
+  if (din == DT_BF16) return launch_tiled<MmaBF16, OUT, mxs_offers>(p, tile, s);
+  if (din == DT_F16) return launch_tiled<MmaF16, OUT, mxs_offers>(p, tile, s);
+  if (din == DT_FP8 && scaled) return launch_tiled<MmaMXS, OUT, mxs_offers>(p, tile, s);
+  if (din == DT_FP4 && scaled) return launch_tiled<MmaMX4S, OUT, mxs_offers>(p, tile, s);
   return hipErrorInvalidValue;
 }
 

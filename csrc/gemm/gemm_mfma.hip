@@ -81,8 +81,37 @@ int choose_tile(int64_t M, int64_t N, int64_t K, int din) {
   return TILE_128x128;
 }
 
+// Block-scale operands as every scaled flavour of the tiled kernel reads them: both present, base
+// and row stride multiples of `align` (the scales of a row's K-tile are one aligned 32-bit load,
+// align 4; 64-bit for fp4 data, align 8), a row's K / 32 bytes within its stride, rows addressed
+// by 32-bit byte offsets.
+static bool scale_operands_ok(const GemmArgs& p, int align) {
+  return p.a_scale != nullptr && p.b_scale != nullptr &&
+         (((uintptr_t)p.a_scale | (uintptr_t)p.b_scale) & (align - 1)) == 0 &&
+         p.a_scale_ld % align == 0 && p.b_scale_ld % align == 0 && p.a_scale_ld >= p.K / 32 &&
+         p.b_scale_ld >= p.K / 32 && (int64_t)p.M * p.a_scale_ld < (int64_t(1) << 31) &&
+         (int64_t)p.N * p.b_scale_ld < (int64_t(1) << 31);
+}
+
+// The block-scaled and quantising flavours address plain operands only: no K-split, A row table,
+// grouped A rows, arrival flags or in-kernel all-gather. `refusal` is the caller's code for it.
+// What differs between the callers (a_grp / c_grp already defaulted by gemm_launch):
+//  * plain_c_rows: grouped C rows are refused too (the quantising epilogue writes plain rows);
+//  * plain_c_order: a C row table and a tile order are refused too (fp4 operands and quantised
+//    output; fp8 operands with scales take both, as the tiled kernel does with unit scales).
+static hipError_t plain_operands_only(const GemmArgs& p, bool plain_c_rows, bool plain_c_order,
+                                      hipError_t refusal) {
+  const int64_t rows = p.M > 0 ? p.M : 1;
+  if (p.ksplit > 1 || p.a_table != nullptr || p.a_grp != rows || p.flags != nullptr ||
+      p.ag_ctas > 0 || p.ag_mode != 0)
+    return refusal;
+  if (plain_c_rows && p.c_grp != rows) return refusal;
+  if (plain_c_order && (p.c_table != nullptr || p.tile_order != 0)) return refusal;
+  return hipSuccess;
+}
+
 // DT_FP4 operands: the block-scaled MXFP4 flavour of the tiled kernel or hipErrorInvalidValue,
-// never a launch with something substituted. (a_grp / c_grp already defaulted by gemm_launch.)
+// never a launch with something substituted.
 static hipError_t gemm_launch_fp4(const GemmArgs& p, int dout, int tile, int mode, hipStream_t s) {
   if (p.a_scale == nullptr || p.b_scale == nullptr) return hipErrorInvalidValue;
   if (dout != DT_BF16 && dout != DT_F16 && dout != DT_F32) return hipErrorInvalidValue;
@@ -91,33 +120,21 @@ static hipError_t gemm_launch_fp4(const GemmArgs& p, int dout, int tile, int mod
   if (p.M < 0 || p.N < 0 || p.K <= 0 || p.K % 256 || p.lda % 2 || p.ldb % 2 || p.lda < p.K ||
       p.ldb < p.K)
     return hipErrorInvalidValue;
-  if (p.ksplit > 1 || p.a_table != nullptr || p.a_grp != (p.M > 0 ? p.M : 1) ||
-      p.flags != nullptr || p.ag_ctas > 0 || p.ag_mode != 0 || p.c_table != nullptr ||
-      p.tile_order != 0)
-    return hipErrorInvalidValue;
+  const hipError_t e = plain_operands_only(p, false, true, hipErrorInvalidValue);
+  if (e != hipSuccess) return e;
   if (p.M == 0 || p.N == 0) return hipSuccess;
   // the fast path's alignment, on the operands as the byte matrices the kernel reads
-  GemmArgs q = p;
-  q.K = p.K / 2;
-  q.lda = p.lda / 2;
-  q.ldb = p.ldb / 2;
   if (p.a == nullptr || p.b == nullptr || p.c == nullptr || p.ldc < p.N ||
-      !gemm_fast_path_ok(q, DT_U8, dout))
+      !gemm_fast_path_ok(fp4_byte_view(p, true, false), DT_U8, dout))
     return hipErrorInvalidValue;
-  // one aligned 64-bit load per row and K-tile, rows addressed by 32-bit byte offsets
-  if ((((uintptr_t)p.a_scale | (uintptr_t)p.b_scale) & 7) || p.a_scale_ld % 8 ||
-      p.b_scale_ld % 8 || p.a_scale_ld < p.K / 32 || p.b_scale_ld < p.K / 32 ||
-      (int64_t)p.M * p.a_scale_ld >= (int64_t(1) << 31) ||
-      (int64_t)p.N * p.b_scale_ld >= (int64_t(1) << 31))
-    return hipErrorInvalidValue;
+  if (!scale_operands_ok(p, 8)) return hipErrorInvalidValue;
   if (tile == TILE_AUTO) tile = mxs_tile_for(choose_tile(p.M, p.N, p.K, DT_FP4));
   if (tile < 0) return hipErrorInvalidValue;
   return launch_fast_mx4(p, dout, tile, s);
 }
 
 // Quantised output (dout = DT_FP8 / DT_FP4 with GemmArgs::c_scale): the tiled kernel's quantising
-// epilogue or hipErrorInvalidValue, never a launch with something substituted. (a_grp / c_grp
-// already defaulted by gemm_launch.)
+// epilogue or hipErrorInvalidValue, never a launch with something substituted.
 static hipError_t gemm_launch_qout(const GemmArgs& p, int din, int dout, int tile, int mode,
                                    hipStream_t s) {
   const bool q4 = dout == DT_FP4, in4 = din == DT_FP4;
@@ -134,34 +151,19 @@ static hipError_t gemm_launch_qout(const GemmArgs& p, int din, int dout, int til
   if (tile != TILE_AUTO && !mxs_offers(tile)) return hipErrorInvalidValue;
   // whole 32-column blocks, as many as the GEMM that reads them takes per K-tile row
   if (p.M < 0 || p.N < 0 || p.K <= 0 || p.N % (q4 ? 256 : 128)) return hipErrorInvalidValue;
-  if (p.ksplit > 1 || p.a_table != nullptr || p.a_grp != (p.M > 0 ? p.M : 1) ||
-      p.c_grp != (p.M > 0 ? p.M : 1) || p.flags != nullptr || p.ag_ctas > 0 || p.ag_mode != 0 ||
-      p.c_table != nullptr || p.tile_order != 0)
-    return hipErrorInvalidValue;
+  const hipError_t e = plain_operands_only(p, true, true, hipErrorInvalidValue);
+  if (e != hipSuccess) return e;
   if (p.M == 0 || p.N == 0) return hipSuccess;
   // the fast path's alignment, on operands and output as the byte matrices the kernel touches;
   // output rows 16-byte aligned: what the GEMM that reads them as its A asks for
-  GemmArgs q = p;
-  if (in4) {
-    if (p.K % 256 || p.lda % 2 || p.ldb % 2) return hipErrorInvalidValue;
-    q.K = p.K / 2;
-    q.lda = p.lda / 2;
-    q.ldb = p.ldb / 2;
-  }
+  if (in4 && (p.K % 256 || p.lda % 2 || p.ldb % 2)) return hipErrorInvalidValue;
   if (q4 && p.ldc % 2) return hipErrorInvalidValue;
-  q.ldc = q4 ? p.ldc / 2 : p.ldc;
+  const GemmArgs q = fp4_byte_view(p, in4, q4);
   if (p.a == nullptr || p.b == nullptr || p.c == nullptr || p.lda < p.K || p.ldb < p.K ||
       p.ldc < p.N || q.ldc % 16 || ((uintptr_t)p.c & 15) ||
       !gemm_fast_path_ok(q, in4 ? DT_U8 : din, DT_U8))
     return hipErrorInvalidValue;
-  if (scaled) {  // one aligned 32-bit (fp4: 64-bit) load per row and K-tile, 32-bit row offsets
-    const int al = in4 ? 8 : 4;
-    if ((((uintptr_t)p.a_scale | (uintptr_t)p.b_scale) & (al - 1)) || p.a_scale_ld % al ||
-        p.b_scale_ld % al || p.a_scale_ld < p.K / 32 || p.b_scale_ld < p.K / 32 ||
-        (int64_t)p.M * p.a_scale_ld >= (int64_t(1) << 31) ||
-        (int64_t)p.N * p.b_scale_ld >= (int64_t(1) << 31))
-      return hipErrorInvalidValue;
-  }
+  if (scaled && !scale_operands_ok(p, in4 ? 8 : 4)) return hipErrorInvalidValue;
   // the output scales in the layout their reader takes (4-byte words; 8 for fp4 data)
   const int cal = q4 ? 8 : 4;
   if (((uintptr_t)p.c_scale & (cal - 1)) || p.c_scale_ld % cal || p.c_scale_ld < p.N / 32 ||
@@ -189,14 +191,8 @@ hipError_t gemm_launch(const GemmArgs& p_in, int din, int dout, int tile, int mo
   const bool scaled = p.a_scale != nullptr;
   if (scaled && p.M != 0 && p.N != 0) {
     if (din != DT_FP8 || mode == GEMM_MODE_GENERIC || (tile != TILE_AUTO && !mxs_offers(tile)) ||
-        p.a_grp != p.M || p.a_table != nullptr || p.flags != nullptr || p.ag_ctas > 0 ||
-        p.ag_mode != 0 || p.ksplit > 1 || !gemm_fast_path_ok(p, din, dout))
-      return hipErrorNotSupported;
-    // one aligned 32-bit word per row and K-tile, rows addressed by 32-bit byte offsets
-    if ((((uintptr_t)p.a_scale | (uintptr_t)p.b_scale) & 3) || p.a_scale_ld % 4 ||
-        p.b_scale_ld % 4 || p.a_scale_ld < p.K / 32 || p.b_scale_ld < p.K / 32 ||
-        (int64_t)p.M * p.a_scale_ld >= (int64_t(1) << 31) ||
-        (int64_t)p.N * p.b_scale_ld >= (int64_t(1) << 31))
+        plain_operands_only(p, false, false, hipErrorNotSupported) != hipSuccess ||
+        !gemm_fast_path_ok(p, din, dout) || !scale_operands_ok(p, 4))
       return hipErrorNotSupported;
     mode = GEMM_MODE_MX;
   }

@@ -4,9 +4,6 @@
 
 namespace ddlb {
 hipError_t launch_fast_mx(const GemmArgs& p, int dout, int tile, hipStream_t s) {
-  if (dout == DT_BF16) return launch_mx_cfg<DT_BF16>(p, tile, s);
-  if (dout == DT_F16) return launch_mx_cfg<DT_F16>(p, tile, s);
-  if (dout == DT_F32) return launch_mx_cfg<DT_F32>(p, tile, s);
-  return hipErrorInvalidValue;
+  return dispatch_out(dout, [&](auto o) { return launch_mx_cfg<decltype(o)::value>(p, tile, s); });
 }
 }  // namespace ddlb

@@ -4,9 +4,9 @@
 
 namespace ddlb {
 hipError_t launch_fast_mxs(const GemmArgs& p, int dout, int tile, hipStream_t s) {
-  if (dout == DT_BF16) return launch_mxs_cfg<DT_BF16>(p, tile, s);
-  if (dout == DT_F16) return launch_mxs_cfg<DT_F16>(p, tile, s);
-  if (dout == DT_F32) return launch_mxs_cfg<DT_F32>(p, tile, s);
-  return hipErrorInvalidValue;
+  // gemm_launch has checked the operands and mapped the tile code (mxs_tile_for)
+  return dispatch_out(dout, [&](auto o) {
+    return launch_tiled<MmaMXS, decltype(o)::value, mxs_offers>(p, tile, s);
+  });
 }
 }  // namespace ddlb

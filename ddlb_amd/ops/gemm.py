@@ -17,7 +17,7 @@ data and E8M0 scales per 32 output columns, quantised in the GEMM's epilogue.
 
 from __future__ import annotations
 
-from typing import Optional
+from typing import NamedTuple, Optional
 
 from ddlb_amd.ops import load
 
@@ -55,17 +55,23 @@ def default_out_dtype(in_dtype):
     return torch.bfloat16 if in_dtype == torch.float8_e4m3fn else in_dtype
 
 
+def _check_placement(*ts):
+    """Where the operands live and how they are laid out: ROCm device tensors on one device, 2-D,
+    unit inner stride."""
+    if any(t.device.type != "cuda" for t in ts):
+        raise ValueError("native GEMM operands must be ROCm device tensors")
+    if any(t.device != ts[0].device for t in ts):
+        raise ValueError("operands on different devices")
+    if any(t.dim() != 2 for t in ts):
+        raise ValueError("native GEMM expects 2-D operands")
+    if any(t.stride(1) != 1 for t in ts):
+        raise ValueError("operands must be row-major with unit inner stride")
+
+
 def _check_operands(a, w, out, M, a_rows_phys):
     import torch
 
-    if a.device.type != "cuda" or w.device.type != "cuda" or out.device.type != "cuda":
-        raise ValueError("native GEMM operands must be ROCm device tensors")
-    if not (a.device == w.device == out.device):
-        raise ValueError("operands on different devices")
-    if a.dim() != 2 or w.dim() != 2 or out.dim() != 2:
-        raise ValueError("native GEMM expects 2-D operands")
-    if a.stride(1) != 1 or w.stride(1) != 1 or out.stride(1) != 1:
-        raise ValueError("operands must be row-major with unit inner stride")
+    _check_placement(a, w, out)
     if a.dtype != w.dtype:
         raise TypeError(f"A dtype {a.dtype} != W dtype {w.dtype}")
     if a.shape[1] != w.shape[1]:
@@ -119,7 +125,7 @@ def split_k_factor(M: int, N: int, K: int, esz: int, ncu: int = 0) -> int:
 
 
 SCALED_TILES = ("256x128", "128x256", "128x128", "256x128w4")  # gemm.h mxs_offers()
-SCALED_FP4_TILES = ("256x128", "128x256", "128x128", "256x128w4")  # gemm.h mx4_offers()
+SCALED_FP4_TILES = SCALED_TILES  # gemm.h mx4_offers()
 
 
 def _fp4_dtype():
@@ -131,6 +137,57 @@ def _fp4_dtype():
 def _is_fp4(t) -> bool:
     dt = _fp4_dtype()
     return dt is not None and getattr(t, "dtype", None) == dt
+
+
+class _ScaledFormat(NamedTuple):
+    """What the two block-scaled operand formats differ in, wording of the refusals included."""
+    per_byte: int   # elements per stored element: K = per_byte * a.shape[1]
+    kmod: int       # K is a whole number of 128-byte K-tiles
+    align: int      # scale base and row stride: the scales of a row's K-tile are one aligned load
+    tiles: tuple
+    noun: str       # the subject of the messages ...
+    plural: bool    # ... and its number
+    runs: str       # the subject of the mode message
+    tile_note: str
+
+
+_MX_FP8 = _ScaledFormat(1, 128, 4, SCALED_TILES, "block scales", True, "block scales",
+                        " (the ping-pong kernels t8 / pt8 / t4 / pt4 take unit scales)")
+_MX_FP4 = _ScaledFormat(2, 256, 8, SCALED_FP4_TILES, "the fp4 GEMM", False, "fp4 operands", "")
+
+
+def _check_block_scaled(f, a, w, a_scale, w_scale, M, tile, mode, a_grp, ksplit):
+    """The refusals the block-scaled formats share, before anything is launched."""
+    import torch
+
+    be, need, do = (("are", "need", "do") if f.plural else ("is", "needs", "does"))
+    if mode not in ("auto", "mx"):
+        raise ValueError(f"{f.runs} run the MX kernel (mode auto / mx), not mode={mode!r}")
+    if tile != "auto" and tile not in f.tiles:
+        raise ValueError(f"{f.noun} {be} offered for tile auto / {f.tiles}, not "
+                         f"{tile!r}{f.tile_note}")
+    if a_grp not in (0, M):
+        raise ValueError(f"{f.noun} {need} plain A rows (no grouped A rows)")
+    if ksplit > 1:
+        raise ValueError(f"{f.noun} {do} not combine with a K-split")
+    K = f.per_byte * a.shape[1]
+    if K % f.kmod:
+        raise ValueError(f"{f.noun} {need} K % {f.kmod} == 0 (K = {K})")
+    for name, sc, rows in (("a_scale", a_scale, a.shape[0]), ("w_scale", w_scale, w.shape[0])):
+        if not isinstance(sc, torch.Tensor) or sc.dtype != torch.uint8:
+            raise TypeError(f"{name} must be a uint8 tensor of E8M0 bytes")
+        if sc.device != a.device:
+            raise ValueError(f"{name} is on {sc.device}, the operands on {a.device}")
+        if tuple(sc.shape) != (rows, K // 32):
+            raise ValueError(f"{name} must have shape {(rows, K // 32)}, not {tuple(sc.shape)}")
+        if sc.stride(1) != 1 or sc.stride(0) % f.align or sc.stride(0) < K // 32:
+            raise ValueError(f"{name} needs unit inner stride and a row stride that is a "
+                             f"multiple of {f.align} (strides {tuple(sc.stride())})")
+        if sc.data_ptr() % f.align:
+            raise ValueError(f"{name} must start at {'an' if f.align == 8 else 'a'} "
+                             f"{f.align}-byte-aligned address")
+        if rows * sc.stride(0) >= 2 ** 31:
+            raise ValueError(f"{name} spans 2 GiB or more")
 
 
 def _check_fp4(a, w, out, a_scale, w_scale, M, tile, mode, a_grp, ksplit):
@@ -145,68 +202,18 @@ def _check_fp4(a, w, out, a_scale, w_scale, M, tile, mode, a_grp, ksplit):
                          "unit-scale kernel)")
     if out.dtype not in (torch.bfloat16, torch.float16, torch.float32):
         raise TypeError("fp4 GEMM output must be bf16, f16 or f32")
-    if mode not in ("auto", "mx"):
-        raise ValueError(f"fp4 operands run the MX kernel (mode auto / mx), not mode={mode!r}")
-    if tile != "auto" and tile not in SCALED_FP4_TILES:
-        raise ValueError(f"the fp4 GEMM is offered for tile auto / {SCALED_FP4_TILES}, not "
-                         f"{tile!r}")
-    if a_grp not in (0, M):
-        raise ValueError("the fp4 GEMM needs plain A rows (no grouped A rows)")
-    if ksplit > 1:
-        raise ValueError("the fp4 GEMM does not combine with a K-split")
-    K = 2 * a.shape[1]
-    if K % 256:
-        raise ValueError(f"the fp4 GEMM needs K % 256 == 0 (K = {K})")
-    for name, sc, rows in (("a_scale", a_scale, a.shape[0]), ("w_scale", w_scale, w.shape[0])):
-        if not isinstance(sc, torch.Tensor) or sc.dtype != torch.uint8:
-            raise TypeError(f"{name} must be a uint8 tensor of E8M0 bytes")
-        if sc.device != a.device:
-            raise ValueError(f"{name} is on {sc.device}, the operands on {a.device}")
-        if tuple(sc.shape) != (rows, K // 32):
-            raise ValueError(f"{name} must have shape {(rows, K // 32)}, not {tuple(sc.shape)}")
-        if sc.stride(1) != 1 or sc.stride(0) % 8 or sc.stride(0) < K // 32:
-            raise ValueError(f"{name} needs unit inner stride and a row stride that is a "
-                             f"multiple of 8 (strides {tuple(sc.stride())})")
-        if sc.data_ptr() % 8:
-            raise ValueError(f"{name} must start at an 8-byte-aligned address")
-        if rows * sc.stride(0) >= 2 ** 31:
-            raise ValueError(f"{name} spans 2 GiB or more")
+    _check_block_scaled(_MX_FP4, a, w, a_scale, w_scale, M, tile, mode, a_grp, ksplit)
 
 
 def _check_scales(a, w, a_scale, w_scale, M, tile, mode, a_grp, ksplit):
-    """Every refusal of the block-scaled GEMM, before anything is launched."""
+    """Every refusal of the block-scaled fp8 GEMM, before anything is launched."""
     import torch
 
     if (a_scale is None) != (w_scale is None):
         raise ValueError("a_scale and w_scale go together: pass both or neither")
     if a.dtype != torch.float8_e4m3fn:
         raise TypeError(f"block scales need float8_e4m3fn operands, not {a.dtype}")
-    if mode not in ("auto", "mx"):
-        raise ValueError(f"block scales run the MX kernel (mode auto / mx), not mode={mode!r}")
-    if tile != "auto" and tile not in SCALED_TILES:
-        raise ValueError(f"block scales are offered for tile auto / {SCALED_TILES}, not "
-                         f"{tile!r} (the ping-pong kernels t8 / pt8 / t4 / pt4 take unit scales)")
-    if a_grp not in (0, M):
-        raise ValueError("block scales need plain A rows (no grouped A rows)")
-    if ksplit > 1:
-        raise ValueError("block scales do not combine with a K-split")
-    K = a.shape[1]
-    if K % 128:
-        raise ValueError(f"block scales need K % 128 == 0 (K = {K})")
-    for name, sc, rows in (("a_scale", a_scale, a.shape[0]), ("w_scale", w_scale, w.shape[0])):
-        if not isinstance(sc, torch.Tensor) or sc.dtype != torch.uint8:
-            raise TypeError(f"{name} must be a uint8 tensor of E8M0 bytes")
-        if sc.device != a.device:
-            raise ValueError(f"{name} is on {sc.device}, the operands on {a.device}")
-        if tuple(sc.shape) != (rows, K // 32):
-            raise ValueError(f"{name} must have shape {(rows, K // 32)}, not {tuple(sc.shape)}")
-        if sc.stride(1) != 1 or sc.stride(0) % 4 or sc.stride(0) < K // 32:
-            raise ValueError(f"{name} needs unit inner stride and a row stride that is a "
-                             f"multiple of 4 (strides {tuple(sc.stride())})")
-        if sc.data_ptr() % 4:
-            raise ValueError(f"{name} must start at a 4-byte-aligned address")
-        if rows * sc.stride(0) >= 2 ** 31:
-            raise ValueError(f"{name} spans 2 GiB or more")
+    _check_block_scaled(_MX_FP8, a, w, a_scale, w_scale, M, tile, mode, a_grp, ksplit)
 
 
 OUT_QUANTS = ("mx", "mxfp4")
@@ -226,6 +233,8 @@ def _check_out_quant(a, w, out_quant, out=None, out_scale=None, *, a_scale=None,
     are checked when given. Returns ``(M, N, K)`` in elements."""
     import torch
     from types import SimpleNamespace
+
+    from ddlb_amd.ops.mx import check_quant_pair_layout, check_quant_pair_types
 
     if out_quant not in OUT_QUANTS:
         raise ValueError(f"out_quant must be None or one of {OUT_QUANTS}, not {out_quant!r}")
@@ -284,47 +293,43 @@ def _check_out_quant(a, w, out_quant, out=None, out_scale=None, *, a_scale=None,
     if M >= 2 ** 31 or N >= 2 ** 31 or K >= 2 ** 31:
         raise ValueError("dimensions must fit in 32 bits")
     ncol, sal = (N // 2 if q4 else N), (8 if q4 else 4)
-    if out is not None:
-        if not isinstance(out, torch.Tensor) or out.dtype != qdt:
-            raise TypeError(f"out must be a {qdt} tensor for out_quant={out_quant!r}, not "
-                            f"{getattr(out, 'dtype', type(out))}")
-        if out.device != a.device:
-            raise ValueError(f"out is on {out.device}, the operands on {a.device}")
-        if out.dim() != 2 or out.shape[0] < M or out.shape[1] != ncol:
-            raise ValueError(f"out must have shape (>= {M}, {ncol}), not {tuple(out.shape)}")
-        if out.stride(1) != 1 or out.stride(0) < ncol or out.stride(0) % 16:
-            raise ValueError(f"out needs unit inner stride and a row stride that is a multiple "
-                             f"of 16 bytes (strides {tuple(out.stride())})")
-        if out.data_ptr() % 16:
-            raise ValueError("out must start at a 16-byte-aligned address")
-    if out_scale is not None:
-        if not isinstance(out_scale, torch.Tensor) or out_scale.dtype != torch.uint8:
-            raise TypeError("out_scale must be a uint8 tensor of E8M0 bytes")
-        if out_scale.device != a.device:
-            raise ValueError(f"out_scale is on {out_scale.device}, the operands on {a.device}")
-        if out_scale.dim() != 2 or out_scale.shape[0] < M or out_scale.shape[1] != N // 32:
-            raise ValueError(f"out_scale must have shape (>= {M}, {N // 32}), not "
-                             f"{tuple(out_scale.shape)}")
-        if (out_scale.stride(1) != 1 or out_scale.stride(0) < N // 32
-                or out_scale.stride(0) % sal):
-            raise ValueError(f"out_scale needs unit inner stride and a row stride that is a "
-                             f"multiple of {sal} (strides {tuple(out_scale.stride())})")
-        if M * out_scale.stride(0) >= 2 ** 31:
-            raise ValueError("out_scale spans 2 GiB or more")
-        if out_scale.data_ptr() % sal:
-            raise ValueError(f"out_scale must start at a {sal}-byte-aligned address")
+    check_quant_pair_types(("out", "out_scale"), out, out_scale, qdt, f"out_quant={out_quant!r}")
+    for name, t, cols in (("out", out, ncol), ("out_scale", out_scale, N // 32)):
+        if t is None:
+            continue
+        if t.device != a.device:
+            raise ValueError(f"{name} is on {t.device}, the operands on {a.device}")
+        if t.dim() != 2 or t.shape[0] < M or t.shape[1] != cols:
+            raise ValueError(f"{name} must have shape (>= {M}, {cols}), not {tuple(t.shape)}")
+    check_quant_pair_layout(("out", "out_scale"), out, out_scale, ncol, N // 32, sal)
+    if out_scale is not None and M * out_scale.stride(0) >= 2 ** 31:
+        raise ValueError("out_scale spans 2 GiB or more")
     if M * (N // 32) >= 2 ** 31:
         raise ValueError("out_scale spans 2 GiB or more")
     return M, N, K
 
 
-def _check_quant_operands(a, w):
-    if a.device.type != "cuda" or w.device.type != "cuda":
-        raise ValueError("native GEMM operands must be ROCm device tensors")
-    if a.device != w.device:
-        raise ValueError("operands on different devices")
-    if a.stride(1) != 1 or w.stride(1) != 1:
-        raise ValueError("operands must be row-major with unit inner stride")
+def _launch(C, a, w, c, M, N, K, tile, mode, s, *, a_grp=0, a_gstride=0, c_grp=0, c_gstride=0,
+            act=0, ksplit=None, a_scale=None, w_scale=None, out_scale=None):
+    """The one call of ``C.gemm``: pointers, leading dimensions and dtype codes from the tensors
+    (fp4 data: two elements per stored byte, dimensions go in ELEMENTS), then the optional tail
+    in the extension's positional order: ``ksplit``, the four operand-scale arguments (block
+    scales always run ``mode="mx"``), the two output-scale arguments."""
+    am, cm = (2 if _is_fp4(a) else 1), (2 if _is_fp4(c) else 1)
+    scaled = a_scale is not None
+    args = [a.data_ptr(), w.data_ptr(), c.data_ptr(), am * a.stride(0), am * w.stride(0),
+            cm * c.stride(0), M, N, K, DT_FP4 if am == 2 else dtype_code(a.dtype),
+            DT_FP4 if cm == 2 else dtype_code(c.dtype), TILES[tile],
+            MODES["mx"] if scaled else MODES[mode], a_grp, a_gstride, c_grp, c_gstride, s, act]
+    if ksplit is not None or scaled or out_scale is not None:
+        args.append(1 if ksplit is None else ksplit)
+    if scaled:
+        args += [a_scale.data_ptr(), w_scale.data_ptr(), a_scale.stride(0), w_scale.stride(0)]
+    elif out_scale is not None:
+        args += [0, 0, 0, 0]
+    if out_scale is not None:
+        args += [out_scale.data_ptr(), out_scale.stride(0)]
+    C.gemm(*args)
 
 
 def _gemm_out_quant(a, w, out, out_scale, out_quant, *, out_dtype, tile, mode, M, a_grp, c_grp,
@@ -342,7 +347,7 @@ def _gemm_out_quant(a, w, out, out_scale, out_quant, *, out_dtype, tile, mode, M
     q4 = out_quant == "mxfp4"
     fp4 = _is_fp4(a)
     ncol = N // 2 if q4 else N
-    _check_quant_operands(a, w)
+    _check_placement(a, w)
     # dense rows are what the consumer asks of a / a_scale: N % 128 (256) makes a data row a
     # multiple of 16 bytes and a scale row a multiple of 4 (8)
     if out is None:
@@ -357,16 +362,9 @@ def _gemm_out_quant(a, w, out, out_scale, out_quant, *, out_dtype, tile, mode, M
         raise ValueError("a quantised output needs the MFMA fast path: 16-byte-aligned operand "
                          "rows and K a whole number of 128-byte K-tiles")
     s = stream if stream is not None else torch.cuda.current_stream(a.device).cuda_stream
-    scaled = a_scale is not None
     # (ksplit 1: neither a requested nor the automatic K-split engages on this path)
-    C.gemm(a.data_ptr(), w.data_ptr(), out.data_ptr(),
-           (2 if fp4 else 1) * a.stride(0), (2 if fp4 else 1) * w.stride(0),
-           (2 if q4 else 1) * out.stride(0), M, N, K,
-           DT_FP4 if fp4 else dtype_code(a.dtype), DT_FP4 if q4 else DT_FP8, TILES[tile],
-           MODES["mx"] if scaled else MODES["auto"], 0, 0, 0, 0, s, ACTS[act], 1,
-           a_scale.data_ptr() if scaled else 0, w_scale.data_ptr() if scaled else 0,
-           a_scale.stride(0) if scaled else 0, w_scale.stride(0) if scaled else 0,
-           out_scale.data_ptr(), out_scale.stride(0))
+    _launch(C, a, w, out, M, N, K, tile, mode, s, act=ACTS[act], a_scale=a_scale,
+            w_scale=w_scale, out_scale=out_scale)
     if stream is not None:  # the outputs stay allocated until that stream reaches them
         out.record_stream(torch.cuda.ExternalStream(s))
         out_scale.record_stream(torch.cuda.ExternalStream(s))
@@ -443,10 +441,8 @@ def gemm(a, w, out=None, *, out_dtype=None, tile: str = "auto", mode: str = "aut
                                                K // 2, DT_U8, dtype_code(out.dtype)):
             raise ValueError("the fp4 GEMM needs the MFMA fast path: 16-byte-aligned operand "
                              "rows, 8-byte-aligned output rows")
-        C.gemm(a.data_ptr(), w.data_ptr(), out.data_ptr(), 2 * a.stride(0), 2 * w.stride(0),
-               out.stride(0), M, N, K, DT_FP4, dtype_code(out.dtype), TILES[tile], MODES["mx"],
-               0, 0, c_grp, c_gstride, s, ACTS[act], 1, a_scale.data_ptr(), w_scale.data_ptr(),
-               a_scale.stride(0), w_scale.stride(0))
+        _launch(C, a, w, out, M, N, K, tile, mode, s, c_grp=c_grp, c_gstride=c_gstride,
+                act=ACTS[act], a_scale=a_scale, w_scale=w_scale)
         return out
     if scaled:
         _check_scales(a, w, a_scale, w_scale, M, tile, mode, a_grp, S)
@@ -455,10 +451,8 @@ def gemm(a, w, out=None, *, out_dtype=None, tile: str = "auto", mode: str = "aut
                                                DT_FP8, dtype_code(out.dtype)):
             raise ValueError("block scales need the MFMA fast path: 16-byte-aligned operand "
                              "rows, 8-byte-aligned output rows")
-        C.gemm(a.data_ptr(), w.data_ptr(), out.data_ptr(), a.stride(0), w.stride(0),
-               out.stride(0), M, N, K, DT_FP8, dtype_code(out.dtype), TILES[tile], MODES["mx"],
-               0, 0, c_grp, c_gstride, s, ACTS[act], 1, a_scale.data_ptr(), w_scale.data_ptr(),
-               a_scale.stride(0), w_scale.stride(0))
+        _launch(C, a, w, out, M, N, K, tile, mode, s, c_grp=c_grp, c_gstride=c_gstride,
+                act=ACTS[act], a_scale=a_scale, w_scale=w_scale)
         return out
     if S == 0:
         S = split_k_factor(M, N, K, a.element_size()) if plain and tile == "auto" else 1
@@ -470,9 +464,7 @@ def gemm(a, w, out=None, *, out_dtype=None, tile: str = "auto", mode: str = "aut
             # another kernel runs the slices one after another into output-dtype partials,
             # summed (f32) by a reduce kernel
             part = torch.empty((S, M, N), dtype=out.dtype, device=a.device)
-            C.gemm(a.data_ptr(), w.data_ptr(), part.data_ptr(), a.stride(0), w.stride(0), N, M,
-                   N, K // S, dtype_code(a.dtype), dtype_code(out.dtype), TILES[tile],
-                   MODES[mode], 0, 0, 0, 0, s, 0, S)
+            _launch(C, a, w, part[0], M, N, K // S, tile, mode, s, ksplit=S)
             C.reduce_sum(out.data_ptr(), [part[j].data_ptr() for j in range(S)], M * N,
                          dtype_code(out.dtype), s)
             if stream is not None:
@@ -481,8 +473,7 @@ def gemm(a, w, out=None, *, out_dtype=None, tile: str = "auto", mode: str = "aut
         # every (slice, tile) pair in one launch into f32 partials, summed in slice order and
         # rounded once by the reduce kernel (an unsplit GEMM's rounding)
         ws = torch.empty((S, M, N), dtype=torch.float32, device=a.device)
-        C.gemm(a.data_ptr(), w.data_ptr(), ws.data_ptr(), a.stride(0), w.stride(0), N, M, N,
-               K // S, dtype_code(a.dtype), DT_F32, TILES["pt4"], MODES[mode], 0, 0, 0, 0, s, 0, S)
+        _launch(C, a, w, ws[0], M, N, K // S, "pt4", mode, s, ksplit=S)
         if out.dtype == torch.float32:
             C.reduce_sum(out.data_ptr(), [ws[j].data_ptr() for j in range(S)], M * N, DT_F32, s)
         else:
@@ -491,9 +482,8 @@ def gemm(a, w, out=None, *, out_dtype=None, tile: str = "auto", mode: str = "aut
         if stream is not None:  # the workspace stays allocated until that stream reaches it
             ws.record_stream(torch.cuda.ExternalStream(s))
         return out
-    C.gemm(a.data_ptr(), w.data_ptr(), out.data_ptr(), a.stride(0), w.stride(0), out.stride(0),
-           M, N, K, dtype_code(a.dtype), dtype_code(out.dtype), TILES[tile], MODES[mode],
-           a_grp, a_gstride, c_grp, c_gstride, s, ACTS[act])
+    _launch(C, a, w, out, M, N, K, tile, mode, s, a_grp=a_grp, a_gstride=a_gstride, c_grp=c_grp,
+            c_gstride=c_gstride, act=ACTS[act])
     return out
 
 

@@ -97,43 +97,47 @@ def dequantize_mx(q, s):
                        e.unsqueeze(2)).reshape(R, K)
 
 
-def quantize_mx(x, *, stream=None):
-    """The HIP quantiser: ``x [R, K]`` bf16 / f16 / f32 on a ROCm device -> ``(q, s)`` as
-    :func:`quantize_mx_reference` computes them, on ``stream`` (default: the current one). Every
-    shape / dtype / stride / alignment check happens here, before the launch."""
+def _quantize_rows(x, fp4: bool, stream):
+    """The body of :func:`quantize_mx` / :func:`quantize_mxfp4`: every check, then the launch."""
     import torch
 
     from ddlb_amd.ops import load
     from ddlb_amd.ops.gemm import dtype_code
 
+    name = "quantize_mxfp4" if fp4 else "quantize_mx"
     if not isinstance(x, torch.Tensor):
-        raise TypeError("quantize_mx expects a tensor")
+        raise TypeError(f"{name} expects a tensor")
     if x.dtype not in (torch.bfloat16, torch.float16, torch.float32):
-        raise TypeError(f"quantize_mx takes {IN_DTYPES}, not {x.dtype}")
+        raise TypeError(f"{name} takes {IN_DTYPES}, not {x.dtype}")
     if x.device.type != "cuda":
-        raise ValueError("quantize_mx needs a ROCm device tensor (quantize_mx_reference runs "
-                         "anywhere)")
-    _check_2d(x)
+        raise ValueError(f"{name} needs a ROCm device tensor ({name}_reference runs anywhere)")
+    (_check_2d_fp4 if fp4 else _check_2d)(x)
     R, K = x.shape
     if R >= 2 ** 31 or K >= 2 ** 31:
         raise ValueError("dimensions must fit in 32 bits")
     if x.stride(1) != 1 or (R > 1 and x.stride(0) < K):
-        raise ValueError("quantize_mx needs row-major input with unit inner stride")
+        raise ValueError(f"{name} needs row-major input with unit inner stride")
     if x.data_ptr() % 16 or (x.stride(0) * x.element_size()) % 16:
-        raise ValueError("quantize_mx needs 16-byte-aligned rows")
+        raise ValueError(f"{name} needs 16-byte-aligned rows")
     C = load()
-    q = torch.empty((R, K), dtype=torch.float8_e4m3fn, device=x.device)
-    s = torch.empty((R, K // BLOCK), dtype=torch.uint8, device=x.device)
-    if R == 0:
-        return q, s
-    st = stream if stream is not None else torch.cuda.current_stream(x.device).cuda_stream
-    with torch.cuda.device(x.device):
-        C.mx_quantize(x.data_ptr(), q.data_ptr(), s.data_ptr(), max(x.stride(0), K), K,
-                      K // BLOCK, R, K, dtype_code(x.dtype), st)
-    if stream is not None:  # the outputs stay allocated until that stream reaches them
-        q.record_stream(torch.cuda.ExternalStream(st))
-        s.record_stream(torch.cuda.ExternalStream(st))
-    return q, s
+    q, s = _alloc_quant(R, K, fp4, x.device)
+    if R > 0:
+        st = stream if stream is not None else torch.cuda.current_stream(x.device).cuda_stream
+        with torch.cuda.device(x.device):
+            (C.mxfp4_quantize if fp4 else C.mx_quantize)(
+                x.data_ptr(), q.data_ptr(), s.data_ptr(), max(x.stride(0), K), q.shape[1],
+                K // BLOCK, R, K, dtype_code(x.dtype), st)
+        if stream is not None:  # the outputs stay allocated until that stream reaches them
+            q.record_stream(torch.cuda.ExternalStream(st))
+            s.record_stream(torch.cuda.ExternalStream(st))
+    return q.view(torch.float4_e2m1fn_x2 if fp4 else torch.float8_e4m3fn), s
+
+
+def quantize_mx(x, *, stream=None):
+    """The HIP quantiser: ``x [R, K]`` bf16 / f16 / f32 on a ROCm device -> ``(q, s)`` as
+    :func:`quantize_mx_reference` computes them, on ``stream`` (default: the current one). Every
+    shape / dtype / stride / alignment check happens here, before the launch."""
+    return _quantize_rows(x, False, stream)
 
 
 # ---------------------------------------------------------------- MXFP4 (E2M1 elements)
@@ -216,38 +220,7 @@ def quantize_mxfp4(x, *, stream=None):
     """The HIP quantiser: ``x [R, K]`` bf16 / f16 / f32 on a ROCm device -> ``(q, s)`` as
     :func:`quantize_mxfp4_reference` computes them, on ``stream`` (default: the current one).
     Every shape / dtype / stride / alignment check happens here, before the launch."""
-    import torch
-
-    from ddlb_amd.ops import load
-    from ddlb_amd.ops.gemm import dtype_code
-
-    if not isinstance(x, torch.Tensor):
-        raise TypeError("quantize_mxfp4 expects a tensor")
-    if x.dtype not in (torch.bfloat16, torch.float16, torch.float32):
-        raise TypeError(f"quantize_mxfp4 takes {IN_DTYPES}, not {x.dtype}")
-    if x.device.type != "cuda":
-        raise ValueError("quantize_mxfp4 needs a ROCm device tensor (quantize_mxfp4_reference "
-                         "runs anywhere)")
-    _check_2d_fp4(x)
-    R, K = x.shape
-    if R >= 2 ** 31 or K >= 2 ** 31:
-        raise ValueError("dimensions must fit in 32 bits")
-    if x.stride(1) != 1 or (R > 1 and x.stride(0) < K):
-        raise ValueError("quantize_mxfp4 needs row-major input with unit inner stride")
-    if x.data_ptr() % 16 or (x.stride(0) * x.element_size()) % 16:
-        raise ValueError("quantize_mxfp4 needs 16-byte-aligned rows")
-    C = load()
-    q = torch.empty((R, K // 2), dtype=torch.uint8, device=x.device)
-    s = torch.empty((R, K // BLOCK), dtype=torch.uint8, device=x.device)
-    if R > 0:
-        st = stream if stream is not None else torch.cuda.current_stream(x.device).cuda_stream
-        with torch.cuda.device(x.device):
-            C.mxfp4_quantize(x.data_ptr(), q.data_ptr(), s.data_ptr(), max(x.stride(0), K),
-                             K // 2, K // BLOCK, R, K, dtype_code(x.dtype), st)
-        if stream is not None:  # the outputs stay allocated until that stream reaches them
-            q.record_stream(torch.cuda.ExternalStream(st))
-            s.record_stream(torch.cuda.ExternalStream(st))
-    return q.view(torch.float4_e2m1fn_x2), s
+    return _quantize_rows(x, True, stream)
 
 
 # ---------------------------------------------------------------- transposed quantisation
@@ -275,6 +248,34 @@ def quantize_mx_t_reference(x, fmt: str = "mx"):
         raise ValueError(f"MX quantisation expects a 2-D tensor, not {tuple(x.shape)}")
     xt = x.t().contiguous()
     return quantize_mxfp4_reference(xt) if fp4 else quantize_mx_reference(xt)
+
+
+def check_quant_pair_types(names, data, scales, qdt, what):
+    """A preallocated (data, scales) pair, either of them optional: ``qdt`` data, uint8 scales.
+    ``names`` are the caller's argument names, ``what`` the format argument it was given."""
+    import torch
+
+    if data is not None and (not isinstance(data, torch.Tensor) or data.dtype != qdt):
+        raise TypeError(f"{names[0]} must be a {qdt} tensor for {what}, not "
+                        f"{getattr(data, 'dtype', type(data))}")
+    if scales is not None and (not isinstance(scales, torch.Tensor)
+                               or scales.dtype != torch.uint8):
+        raise TypeError(f"{names[1]} must be a uint8 tensor of E8M0 bytes")
+
+
+def check_quant_pair_layout(names, data, scales, ncol, nblk, sal):
+    """The rows of such a pair as the GEMM that reads them asks: unit inner stride, data rows of
+    ``ncol`` bytes 16-byte aligned, scale rows of ``nblk`` bytes aligned to ``sal`` (4; 8 beside
+    fp4 data), bases included."""
+    for name, t, cols, mod, unit in ((names[0], data, ncol, 16, " bytes"),
+                                     (names[1], scales, nblk, sal, "")):
+        if t is None:
+            continue
+        if t.stride(1) != 1 or t.stride(0) < cols or t.stride(0) % mod:
+            raise ValueError(f"{name} needs unit inner stride and a row stride that is a "
+                             f"multiple of {mod}{unit} (strides {tuple(t.stride())})")
+        if t.data_ptr() % mod:
+            raise ValueError(f"{name} must start at a {mod}-byte-aligned address")
 
 
 def _check_quant_t(x, fmt: str, out=None, *, two_way: bool = False):
@@ -318,27 +319,14 @@ def _check_quant_t(x, fmt: str, out=None, *, two_way: bool = False):
             raise TypeError("out must be a pair (qt, st)")
         qt, st = out
         qdt = torch.float4_e2m1fn_x2 if fp4 else torch.float8_e4m3fn
-        if not isinstance(qt, torch.Tensor) or qt.dtype != qdt:
-            raise TypeError(f"out[0] must be a {qdt} tensor for fmt={fmt!r}, not "
-                            f"{getattr(qt, 'dtype', type(qt))}")
-        if not isinstance(st, torch.Tensor) or st.dtype != torch.uint8:
-            raise TypeError("out[1] must be a uint8 tensor of E8M0 bytes")
+        check_quant_pair_types(("out[0]", "out[1]"), qt, st, qdt, f"fmt={fmt!r}")
         if qt.device != x.device or st.device != x.device:
             raise ValueError(f"out is on {qt.device} / {st.device}, x on {x.device}")
         if tuple(qt.shape) != (C, ncol):
             raise ValueError(f"out[0] must have shape {(C, ncol)}, not {tuple(qt.shape)}")
         if tuple(st.shape) != (C, R // BLOCK):
             raise ValueError(f"out[1] must have shape {(C, R // BLOCK)}, not {tuple(st.shape)}")
-        if qt.stride(1) != 1 or qt.stride(0) < ncol or qt.stride(0) % 16:
-            raise ValueError(f"out[0] needs unit inner stride and a row stride that is a "
-                             f"multiple of 16 bytes (strides {tuple(qt.stride())})")
-        if qt.data_ptr() % 16:
-            raise ValueError("out[0] must start at a 16-byte-aligned address")
-        if st.stride(1) != 1 or st.stride(0) < R // BLOCK or st.stride(0) % sal:
-            raise ValueError(f"out[1] needs unit inner stride and a row stride that is a "
-                             f"multiple of {sal} (strides {tuple(st.stride())})")
-        if st.data_ptr() % sal:
-            raise ValueError(f"out[1] must start at a {sal}-byte-aligned address")
+        check_quant_pair_layout(("out[0]", "out[1]"), qt, st, ncol, R // BLOCK, sal)
         if C * qt.stride(0) >= 2 ** 31 or C * st.stride(0) >= 2 ** 31:
             raise ValueError("out spans 2 GiB or more")
     if C * ncol >= 2 ** 31:

@@ -258,6 +258,38 @@ def test_unit_scales_equal_the_integer_product():
                            want), tile
 
 
+def _padded(t, pad, poison):
+    """``t`` (one-byte elements) as a view of a buffer whose rows are ``pad`` bytes longer, the
+    padding filled with ``poison``."""
+    buf = torch.full((t.shape[0], t.shape[1] + pad), poison, dtype=torch.uint8, device=t.device)
+    buf[:, :t.shape[1]] = t.view(torch.uint8)
+    return buf[:, :t.shape[1]].view(t.dtype)
+
+
+def test_padded_operand_rows_and_scale_pitch_exact():
+    """fp4 operands and their scales as views of wider buffers (lda > K / 2 bytes, a scale pitch
+    greater than K / 32) with poison in the padding: 6.0 pairs beside the data, NaN bytes beside
+    the scales. Two ragged row tiles, two K-tiles, bf16 out: one rounding of the exact sum."""
+    g = _gen(12)
+    M, N, K = 130, 136, 512
+    nb = K // 32
+    av, wv = _ints((M, K), g), _ints((N, K), g)
+    e_a = torch.randint(-2, 3, (M, nb), generator=g, device=DEV)
+    e_w = torch.randint(-2, 3, (N, nb), generator=g, device=DEV)
+    want = torch.zeros(M, N, dtype=torch.float64, device=DEV)
+    for b in range(nb):
+        p = av[:, 32 * b:32 * b + 32].double() @ wv[:, 32 * b:32 * b + 32].double().t()
+        want += p * pow2_f64(e_a[:, b].unsqueeze(1) + e_w[:, b].unsqueeze(0))
+    want = want.float().to(torch.bfloat16)  # (the sum is exact in f32: 21 bits at the most)
+    a4, w4 = _padded(_pack_ints(av), 32, 0x77), _padded(_pack_ints(wv), 48, 0x77)
+    s_a = _padded((e_a + 127).to(torch.uint8), 8, 0xFF)
+    s_w = _padded((e_w + 127).to(torch.uint8), 16, 0xFF)
+    assert a4.stride(0) == K // 2 + 32 and s_a.stride(0) == nb + 8
+    for tile in ("auto", "128x128"):
+        got = _scaled(a4, w4, s_a, s_w, tile=tile, out_dtype=torch.bfloat16)
+        assert torch.equal(got, want), tile
+
+
 def test_scaled_gemm_keeps_epilogue_and_c_rows():
     """Grouped C rows and the fused activation ride along (the tiled kernel carries them)."""
     a4, w4, s_a, s_w = _single_block_case(256, 128, 256, 9)

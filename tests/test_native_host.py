@@ -33,6 +33,33 @@ def test_tile_maps_host_asan_ubsan(tmp_path):
     assert "tile maps ok" in r.stdout
 
 
+@pytest.mark.skipif(not os.path.exists(HIPCC) and shutil.which("hipcc") is None,
+                    reason="hipcc not installed")
+def test_gemm_dispatch_host_asan_ubsan(tmp_path):
+    """Everything gemm_launch (csrc/gemm/gemm_mfma.hip) decides before a kernel runs, against stub
+    launch entries: entry, tile, GemmArgs, refusal codes, K-split slices, over every family it
+    distinguishes and one perturbation at a time. The table was generated before the host path
+    was refactored and is compared byte for byte."""
+    hipcc = HIPCC if os.path.exists(HIPCC) else shutil.which("hipcc")
+    exe = str(tmp_path / "gemm_dispatch")
+    cmd = [hipcc, "-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", "-g",
+           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+           "-fno-omit-frame-pointer", f"-I{os.path.join(ROOT, 'csrc')}",
+           os.path.join(ROOT, "tests", "native", "test_gemm_dispatch.cpp"), "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-4000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:verify_asan_link_order=0",
+               UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, timeout=300, env=env)
+    assert r.returncode == 0, (r.stdout[-2000:] + r.stderr[-4000:]).decode(errors="replace")
+    with open(os.path.join(ROOT, "tests", "native", "gemm_dispatch_expected.txt"), "rb") as f:
+        expected = f.read()
+    if r.stdout != expected:
+        got, want = r.stdout.splitlines(), expected.splitlines()
+        diff = [(g, w) for g, w in zip(got, want) if g != w][:5]
+        raise AssertionError(f"{len(got)} lines, expected {len(want)}; first differences: {diff}")
+
+
 def test_op_word_layout_matches_native():
     """The Python plan encoder and the C++ executor agree on the op size (csrc/runtime/plan.h
     kOpWords); a mismatch would shift every op's fields. Skipped when the extension is not built."""

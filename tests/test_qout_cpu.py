@@ -236,7 +236,7 @@ def test_automatic_k_split_does_not_engage(monkeypatch):
     """A shape for which a plain bf16 GEMM would split K runs as ONE quantising launch."""
     rec = _Recorder()
     monkeypatch.setattr(G, "load", lambda: rec)
-    monkeypatch.setattr(G, "_check_quant_operands", lambda *a, **k: None)
+    monkeypatch.setattr(G, "_check_placement", lambda *a, **k: None)
     monkeypatch.setattr(torch.cuda, "current_stream",
                         lambda dev=None: types.SimpleNamespace(cuda_stream=0))
     m, n, k = 256, 256, 2048

@@ -9,7 +9,7 @@ import itertools
 import pytest
 import torch
 
-from _exact import ints
+from _exact import ints, pow2_f64
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -123,6 +123,45 @@ def test_exact_sweep(tile, form, fmt):
     assert q.is_contiguous() and s.is_contiguous()
     _, q_ref, s_ref = _oracle(a, w, fmt, **kw)
     _same(q, s, q_ref, s_ref)
+
+
+def _padded(t, pad, poison):
+    """``t`` (one-byte elements) as a view of a buffer whose rows are ``pad`` bytes longer, the
+    padding filled with ``poison``."""
+    buf = torch.full((t.shape[0], t.shape[1] + pad), poison, dtype=torch.uint8, device=DEV)
+    buf[:, :t.shape[1]] = _bytes(t)
+    return buf[:, :t.shape[1]].view(t.dtype)
+
+
+def test_padded_fp4_operand_rows_and_scale_pitch_exact():
+    """fp4 -> mxfp4 with the operands and their scales as views of wider buffers (lda > K / 2
+    bytes, a scale pitch greater than K / 32; 6.0 pairs and NaN bytes in the padding) and the
+    outputs as views as well: two ragged row tiles, two K-tiles. The accumulator is the exact
+    sum (integers times powers of two, 21 bits at the most), so the specification is the
+    reference quantiser on it."""
+    from ddlb_amd.ops.gemm import gemm
+
+    g = _gen(900)
+    M, N, K = 130, 256, 512
+    nb = K // 32
+    av, wv = ints((M, K), torch.float32, g), ints((N, K), torch.float32, g)
+    s_a, s_w = _scale_bytes(M, K, g), _scale_bytes(N, K, g)
+    c = torch.zeros(M, N, dtype=torch.float64, device=DEV)
+    for b in range(nb):
+        p = av[:, 32 * b:32 * b + 32].double() @ wv[:, 32 * b:32 * b + 32].double().t()
+        c += p * pow2_f64(s_a[:, b].long().unsqueeze(1) + s_w[:, b].long().unsqueeze(0) - 254)
+    q_ref, s_ref = _qref("mxfp4")(c.float())
+    a4, w4 = _padded(_pack_ints(av), 32, 0x77), _padded(_pack_ints(wv), 48, 0x77)
+    sa, sw = _padded(s_a, 8, 0xFF), _padded(s_w, 16, 0xFF)
+    assert a4.stride(0) == K // 2 + 32 and sa.stride(0) == nb + 8
+    for tile in ("auto", "128x128"):
+        qb, sb, out, out_scale = _views("mxfp4", M, N)
+        q, s = gemm(a4, w4, out, tile=tile, out_quant="mxfp4", out_scale=out_scale, a_scale=sa,
+                    w_scale=sw)
+        torch.cuda.synchronize()
+        _same(q, s, q_ref, s_ref)
+        _untouched(qb, M, N // 2)
+        _untouched(sb, M, N // 32)
 
 
 # ------------------------------------------------------------------ 2. all 32 block positions
