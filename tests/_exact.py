@@ -7,7 +7,14 @@ it exactly whatever the order of the additions: the specification of a GEMM on s
 
 Operands come as views of larger buffers whose padding holds ``POISON`` (a read outside the view
 changes the result) and outputs as views of buffers filled with ``SENTINEL`` (a write outside the
-view is seen by :func:`untouched`)."""
+view is seen by :func:`untouched`).
+
+The far-offset tests (``tests/test_far_offsets_gpu.py``) place one matrix of a case in a *far*
+view: rows megabytes apart behind a 2 GiB front guard (:func:`far_backing`, :func:`far_view`,
+:func:`far_out`, :func:`untouched_far`), on leading dimensions that :func:`gate_ld` takes from the
+Python copies of the host-side gates below, never from literals."""
+
+import math
 
 import torch
 
@@ -109,3 +116,199 @@ def extreme_scales(M, N, K, gen):
     e_a = (D.unsqueeze(0) + u).clamp(-127, 127)
     e_w = (-D.unsqueeze(0) + v).clamp(-127, 127)
     return (e_a + 127).to(torch.uint8), (e_w + 127).to(torch.uint8), e_a, e_w
+
+
+# ---------------------------------------------------------------------------- far views
+FAR_GUARD = 2 ** 31
+SCAN_CHUNK = 256 << 20    # bytes per scanned piece
+_WORD = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+
+
+def _is_raw(dtype):
+    return dtype == torch.uint8 or dtype == getattr(torch, "float4_e2m1fn_x2", None)
+
+
+def fill_word(value, dtype):
+    """The 8-byte word (as a signed int64 value) that a buffer full of ``value`` in ``dtype``
+    consists of. Byte dtypes (uint8, packed fp4) take ``value & 0xFF``: POISON is byte 5,
+    SENTINEL byte 249."""
+    if _is_raw(dtype):
+        raw = bytes([int(value) & 0xFF])
+    else:
+        one = torch.tensor([float(value)], dtype=torch.float32).to(dtype)
+        raw = bytes(one.view(torch.uint8).tolist())
+    return int.from_bytes(raw * (8 // len(raw)), "little", signed=True)
+
+
+def far_backing(nbytes, guard=FAR_GUARD, device="cuda"):
+    """One ``uint8`` allocation of ``guard + nbytes`` (rounded up to 16): far views start at byte
+    ``guard``, 16-byte aligned; ``backing.guard`` remembers it.
+
+    Why the guard lies in FRONT of the views: a byte offset truncated to 32 bits lands LOWER in
+    the view, and an offset sign-extended from 32 bits lands up to 2 GiB BEFORE the view's base.
+    With the default guard of 2^31 bytes both stay inside this one allocation, so a wrong offset
+    shows as a wrong value or a written sentinel, never as a GPU fault."""
+    assert guard % 16 == 0 and nbytes > 0
+    backing = torch.empty(guard + (nbytes + 15) // 16 * 16, dtype=torch.uint8, device=device)
+    assert backing.data_ptr() % 16 == 0
+    backing.guard = guard
+    return backing
+
+
+def far_span(R, row_bytes, ld_bytes, row0=0):
+    """Bytes from the backing's byte ``guard`` to the end of the last row of such a view."""
+    return (row0 + R - 1) * ld_bytes + row_bytes
+
+
+def far_fill(backing, value, dtype):
+    """The whole backing holds ``value`` in ``dtype`` (in place: no temporary)."""
+    backing.view(torch.int64).fill_(fill_word(value, dtype))
+
+
+def _far_strided(backing, R, C, dtype, ld_bytes, row0):
+    esz = 1 if _is_raw(dtype) else torch.empty((), dtype=dtype).element_size()
+    assert ld_bytes % esz == 0 and ld_bytes >= C * esz, "rows must not overlap"
+    start = backing.guard + row0 * ld_bytes
+    assert start % 16 == 0, "far views are 16-byte aligned"
+    assert backing.guard + far_span(R, C * esz, ld_bytes, row0) <= backing.numel(), \
+        f"the backing of {backing.numel()} bytes is too small for {R} rows {ld_bytes} apart"
+    typed = backing if _is_raw(dtype) else backing.view(dtype)
+    view = torch.as_strided(typed, (R, C), (ld_bytes // esz, 1), start // esz)
+    assert view.data_ptr() == backing.data_ptr() + start
+    return view
+
+
+def far_view(backing, x, ld_bytes, row0=0, fill=POISON):
+    """``x [R, C]`` as an ``as_strided`` view of ``backing`` whose rows lie ``ld_bytes`` apart,
+    row 0 at byte ``guard + row0 * ld_bytes``. Before ``x`` is written the WHOLE backing is set to
+    ``fill`` in ``x``'s dtype (``POISON``: an operand; ``None``: the backing is left as it is,
+    for a second view of one case)."""
+    R, C = x.shape
+    view = _far_strided(backing, R, C, x.dtype, ld_bytes, row0)
+    if fill is not None:
+        far_fill(backing, fill, x.dtype)
+    view.copy_(x)
+    return view
+
+
+def far_out(backing, R, C, dtype, ld_bytes, row0=0, fill=SENTINEL):
+    """An output view like :func:`far_view`'s, the whole backing (the view included) holding
+    ``SENTINEL`` in ``dtype``."""
+    view = _far_strided(backing, R, C, dtype, ld_bytes, row0)
+    if fill is not None:
+        far_fill(backing, fill, dtype)
+    return view
+
+
+def untouched_far(backing, *views, rows=None):
+    """Assert that every byte of ``backing`` outside the ``[R, C]`` elements of ``views`` (all of
+    one dtype; of their rows ``rows`` when given) still holds ``SENTINEL``. The views' contents
+    are set aside, the views are set to the sentinel, the backing is scanned as raw 64-bit words
+    in pieces of ``SCAN_CHUNK`` bytes (no float or bool copy of any of it), and the
+    contents are put back."""
+    dtype = views[0].dtype
+    assert all(v.dtype == dtype for v in views)
+    word = fill_word(SENTINEL, dtype)
+    words = backing.view(torch.int64)
+    step = SCAN_CHUNK // 8
+    assert SCAN_CHUNK <= 256 << 20
+    sel = slice(None) if rows is None else rows
+    raw = [v if _is_raw(dtype) else v.view(_WORD[v.element_size()]) for v in views]
+    kept = [r[sel].clone() for r in raw]
+    unit = torch.tensor([word], dtype=torch.int64).view(raw[0].dtype)[0].item()
+    for r in raw:
+        r[sel] = unit
+    # min and max of a piece are reductions with no temporary: every word equals the sentinel
+    # word exactly when both do
+    ends = torch.stack([torch.stack(torch.aminmax(words[i:i + step]))
+                        for i in range(0, words.numel(), step)]).cpu()
+    hit = ((ends != word).any(dim=1)).nonzero().flatten().tolist()
+    report = None
+    if hit:
+        i = hit[0] * step
+        j = i + int((words[i:i + step] != word).nonzero()[0])
+        report = (f"8-byte words outside the view were written in {len(hit)} of {ends.shape[0]} "
+                  f"pieces, the first at byte {8 * j - backing.guard:+d} from the view's base")
+    for r, k in zip(raw, kept):
+        r[sel] = k
+    assert report is None, report
+
+
+def rows_distinct(x, ld_bytes, row0=0):
+    """Assert what makes an aliased operand read change the product: the rows of ``x`` are
+    pairwise distinct, and the bytes 2^31 and 2^32 before and behind a row's start are either
+    the start of another row or padding (which holds POISON), never the inside of a row."""
+    R, C = x.shape
+    row_bytes = C * x.element_size()
+    assert int(torch.unique(x.to(torch.float32), dim=0).shape[0]) == R, "two rows are equal"
+    for r in range(R):
+        for d in (-2 ** 32, -2 ** 31, 2 ** 31, 2 ** 32):
+            o = (row0 + r) * ld_bytes + d
+            if o >= 0 and o // ld_bytes - row0 < R:
+                assert o % ld_bytes == 0 or o % ld_bytes >= row_bytes, (r, d)
+
+
+FAR_PITCH = (16 << 20) + 16   # rows from 128 on lie past 2^31, rows from 256 on past 2^32
+FAR_SEED = 20
+# the shapes of tests/test_far_offsets_gpu.py (M, N; W far swaps them): ragged tiled / generic,
+# whole-tile ping-pong, pt4 with a fifth row panel, the gates, the K-split, the scaled GEMMs
+FAR_TILED, FAR_PING, FAR_PT4, FAR_GROUPED = (300, 202), (512, 256), (1280, 256), (768, 256)
+GATE_C, GATE_KSPLIT, GATE_SCALED = (512, 256), (256, 256), (256, 256)
+
+
+def far_operands(M, N, K, dtype, seed=FAR_SEED):
+    """``a [M, K]``, ``w [N, K]`` of the far-offset tests, drawn on the CPU with a fixed seed (the
+    CPU test of their rows and the GPU tests see the same numbers)."""
+    g = torch.Generator(device="cpu").manual_seed(seed + 1000003 * M + 1009 * N + K)
+    return ints((M, K), dtype, g), ints((N, K), dtype, g)
+
+
+# ---------------------------------------------------------------------------- the gates
+WT_LIMIT = 0x7FFFFFF0     # the record count of the kernels' 32-bit buffer descriptors
+PT4_LD_BYTES = 1 << 22    # pt4_ok(): the largest operand row pitch pt4 takes
+
+
+def c_fits_wt(M, N, ldc, osz, c_grp=0, c_gstride=0):
+    """Gate 1, ``c_fits_wt()`` of csrc/gemm/gemm_kernels.h without a C row table: pt4 / t4 store
+    C through 32-bit buffer offsets when every C byte lies below ``WT_LIMIT``."""
+    if M <= 0:
+        return False
+    cg = c_grp if c_grp > 0 else M
+    cgs = c_gstride if c_gstride > 0 else cg
+    last_row = (M - 1) // cg * cgs + (M - 1) % cg
+    return (last_row * ldc + N) * osz < WT_LIMIT
+
+
+def pt4_ld_ok(ld, esz):
+    """Gate 2, the pitch clause of ``pt4_ok()``."""
+    return ld * esz <= PT4_LD_BYTES
+
+
+def ksplit_one_launch(S, M, ldc, osz):
+    """Gate 3, ``launch_pt4()``: pt4 runs the (slice, tile) pairs of a K-split in one launch when
+    the ``S`` partials together stay below ``WT_LIMIT``; at and above, ``gemm_launch`` runs the
+    slices one after another."""
+    return S * M * ldc * osz < WT_LIMIT
+
+
+def scale_rows_ok(rows, scale_ld):
+    """Gate 4, ``scale_operands_ok()`` / the ``c_scale_ld`` check of csrc/gemm/gemm_mfma.hip and
+    their Python twins: the scale rows are addressed by 32-bit byte offsets."""
+    return rows * scale_ld < 2 ** 31
+
+
+def gate_ld(pred, align, hi=2 ** 40):
+    """``(last, next)``: the largest multiple of ``align`` for which the monotone predicate
+    ``pred(ld)`` holds, and the next multiple, for which it does not."""
+    assert pred(align) and not pred(hi // align * align)
+    lo, up = 1, hi // align                 # pred(lo * align), not pred(up * align)
+    while up - lo > 1:
+        mid = (lo + up) // 2
+        lo, up = (mid, up) if pred(mid * align) else (lo, mid)
+    assert pred(lo * align) and not pred(up * align) and up == lo + 1
+    return lo * align, up * align
+
+
+def align_of(nbytes, esz):
+    """Elements per ``nbytes`` bytes (the leading-dimension step that keeps rows so aligned)."""
+    return nbytes // math.gcd(nbytes, esz)

@@ -3,6 +3,7 @@ those tests rely on. Everything here runs on the CPU."""
 
 import torch
 
+import _exact as X
 from _exact import (FP8, POISON, SENTINEL, dequant64, exact, exact64, exact_scaled,
                     extreme_scales, ints, padded, pow2_f64, sentinel_out, untouched)
 
@@ -231,3 +232,169 @@ def test_ksplit_specifications_differ(M):
         assert torch.equal(o16, t16) and torch.equal(o16.float(), f32)
         o32, t32 = ksplit_specs(a16.float(), w16.float(), S, torch.float32)
         assert torch.equal(o32, t32) and torch.equal(o32, f32)
+
+
+# ------------------------------------------------------------------ far views and the gates
+SMALL_GUARD, SMALL_LD = 4096, 1024
+FAR_DTYPES = [torch.bfloat16, torch.float32, FP8, torch.uint8]
+
+
+def _small_backing(R):
+    return X.far_backing(X.far_span(R, SMALL_LD, SMALL_LD), guard=SMALL_GUARD, device="cpu")
+
+
+@pytest.mark.parametrize("dtype", FAR_DTYPES)
+def test_far_view_places_rows_and_poisons_the_rest(dtype):
+    R, C = 9, 40
+    x = ints((R, C), torch.float32, _gen(7)).to(dtype)
+    backing = _small_backing(R + 2)
+    assert backing.dtype == torch.uint8 and backing.numel() == SMALL_GUARD + (R + 2) * SMALL_LD
+    esz = x.element_size()
+    for row0 in (0, 2):
+        v = X.far_view(backing, x, SMALL_LD, row0=row0)
+        assert tuple(v.shape) == (R, C) and v.stride() == (SMALL_LD // esz, 1)
+        assert v.data_ptr() == backing.data_ptr() + SMALL_GUARD + row0 * SMALL_LD
+        assert v.data_ptr() % 16 == 0
+        assert torch.equal(v.view(torch.uint8), x.view(torch.uint8))
+        # everything else, the guard included, holds POISON in the view's dtype
+        typed = backing.view(dtype).clone()
+        poison = torch.tensor([POISON]).to(dtype)
+        rows = typed[SMALL_GUARD // esz:].view(R + 2, SMALL_LD // esz)
+        rows[row0:row0 + R, :C] = poison
+        assert bool((typed.view(torch.uint8) == poison.view(torch.uint8)[0]).all()
+                    if esz == 1 else (typed.float() == POISON).all())
+    with pytest.raises(AssertionError):
+        X.far_view(backing, x, SMALL_LD, row0=3)                    # past the backing's end
+    with pytest.raises(AssertionError):
+        X.far_view(backing, x, C * esz - esz)                       # overlapping rows
+
+
+@pytest.mark.parametrize("dtype", FAR_DTYPES)
+def test_untouched_far_sees_a_misplaced_write(dtype):
+    """A write inside a row's padding, in the guard and one row early, one element each."""
+    R, C = 6, 24
+    esz = torch.empty((), dtype=dtype).element_size()
+    backing = _small_backing(R + 3)
+    view = X.far_out(backing, R, C, dtype, SMALL_LD, row0=1)
+    word = X.fill_word(SENTINEL, dtype)
+    assert bool((backing.view(torch.int64) == word).all())
+    if dtype != torch.uint8:
+        assert bool((backing.view(dtype).float() == SENTINEL).all())
+    result = ints((R, C), torch.float32, _gen(8)).to(dtype)
+    view.copy_(result)
+    X.untouched_far(backing, view)
+    assert torch.equal(view.view(torch.uint8), result.view(torch.uint8))  # put back as it was
+    base = (SMALL_GUARD + SMALL_LD) // esz
+    typed = backing.view(dtype)
+    one = torch.tensor([1.0]).to(dtype)
+    for name, at in (("row padding", base + C), ("row padding", base + 2 * SMALL_LD // esz - 1),
+                     ("guard", 0), ("guard", SMALL_GUARD // esz - 1),
+                     ("one row early", base - SMALL_LD // esz),
+                     ("behind the last row", base + R * SMALL_LD // esz)):
+        was = typed[at].clone()
+        typed[at] = one[0]
+        with pytest.raises(AssertionError, match="outside the view"):
+            X.untouched_far(backing, view)
+        typed[at] = was
+        X.untouched_far(backing, view)
+    # physical rows: the rows between the written ones must hold the sentinel
+    rows = torch.tensor([0, 1, 4, 5])
+    X.far_fill(backing, SENTINEL, dtype)
+    view[rows] = result[rows]
+    X.untouched_far(backing, view, rows=rows)
+    view[2, 3] = one[0]
+    with pytest.raises(AssertionError):
+        X.untouched_far(backing, view, rows=rows)
+    # two views of one backing (the K-split's partials)
+    X.far_fill(backing, SENTINEL, dtype)
+    v0 = X.far_out(backing, 3, C, dtype, SMALL_LD, fill=None)
+    v1 = X.far_out(backing, 3, C, dtype, SMALL_LD, row0=3, fill=None)
+    v0.copy_(result[:3])
+    v1.copy_(result[3:])
+    X.untouched_far(backing, v0, v1)
+    with pytest.raises(AssertionError):
+        X.untouched_far(backing, v0)
+
+
+def test_an_aliased_operand_row_changes_the_product():
+    """Rows pairwise distinct: a kernel that reads row j where row i belongs computes another
+    product, and one that reads the padding reads POISON."""
+    M, N, K = 9, 7, 64
+    a, w = X.far_operands(M, N, K, torch.bfloat16)
+    X.rows_distinct(a, SMALL_LD)
+    backing = _small_backing(M)
+    A = X.far_view(backing, a, SMALL_LD)
+    ref = exact(A, w, torch.float32)
+    assert torch.equal(ref, exact(a, w, torch.float32))
+    for i, j in ((5, 1), (0, 8)):
+        alias = A.clone()
+        alias[i] = A[j]
+        got = exact(alias, w, torch.float32)
+        assert not torch.equal(got[i], ref[i]) and torch.equal(got[i], ref[j])
+    pad = torch.as_strided(A, (M, K), A.stride(), A.storage_offset() + K)   # a row's padding
+    assert bool((pad.float() == POISON).all())
+    assert not torch.equal(exact(pad, w, torch.float32), ref)
+    same = a.clone()
+    same[3] = same[6]
+    with pytest.raises(AssertionError, match="equal"):
+        X.rows_distinct(same, SMALL_LD)
+    with pytest.raises(AssertionError):       # 2^31 behind row 0 lies inside row 4
+        X.rows_distinct(a, (2 ** 31 - 32) // 4)
+
+
+@pytest.mark.parametrize("din", [torch.bfloat16, FP8, torch.float32])
+def test_far_operand_rows_are_distinct_at_the_pitches_used(din):
+    """The operands of every far GEMM case, at the pitch the case places them on."""
+    k = 2 * 128 // torch.empty((), dtype=din).element_size()
+    for (M, N), pitch in ((X.FAR_TILED, X.FAR_PITCH), (X.FAR_PING, X.FAR_PITCH),
+                          (X.FAR_PT4, X.PT4_LD_BYTES), (X.GATE_C, X.PT4_LD_BYTES + 16)):
+        for rows, cols in ((M, N), (N, M)):                          # W far swaps M and N
+            a, w = X.far_operands(rows, cols, k, din)
+            X.rows_distinct(a, pitch)
+            X.rows_distinct(w, pitch)
+            assert (rows - 1) * pitch > 2 ** 32 or rows < 300 or pitch < X.FAR_PITCH
+    assert 127 * X.FAR_PITCH < 2 ** 31 <= 128 * X.FAR_PITCH
+    assert 255 * X.FAR_PITCH < 2 ** 32 <= 256 * X.FAR_PITCH
+    assert 1024 * X.PT4_LD_BYTES == 2 ** 32 and X.FAR_PT4[0] // 256 == 5
+
+
+def test_gate_ld_straddles_every_gate():
+    """``gate_ld`` on the Python copies of gates 1, 3 and 4, for the shapes the GPU tests use: the
+    two leading dimensions lie one aligned step apart on either side of the gate, and the byte
+    counts are where the kernels' 32-bit offsets end."""
+    assert X.gate_ld(lambda v: v <= 100, 8) == (96, 104)
+    assert X.gate_ld(lambda v: v < 96, 8) == (88, 96)
+    M, N = X.GATE_C
+    for osz in (2, 4):                                               # gate 1: bf16 and f32 C
+        al = X.align_of(8, osz)
+        last, nxt = X.gate_ld(lambda ld: X.c_fits_wt(M, N, ld, osz), al)
+        assert nxt == last + al and last % al == 0 and last > N
+        assert X.c_fits_wt(M, N, last, osz) and not X.c_fits_wt(M, N, nxt, osz)
+        assert ((M - 1) * last + N) * osz < X.WT_LIMIT <= ((M - 1) * nxt + N) * osz
+        assert ((M - 1) * nxt + N) * osz < X.WT_LIMIT + (M - 1) * 8
+    # grouped C rows count the skipped rows
+    assert X.c_fits_wt(768, 256, 1024, 2, 256, 2 ** 18) and \
+        not X.c_fits_wt(768, 256, 1024, 2, 256, 2 ** 19)
+    assert not X.c_fits_wt(0, 256, 8, 2)
+    S, (M, N) = 2, X.GATE_KSPLIT                                     # gate 3: f32 partials
+    last, nxt = X.gate_ld(lambda ld: X.ksplit_one_launch(S, M, ld, 4), 2)
+    assert nxt == last + 2 and last > N
+    assert S * M * last * 4 < X.WT_LIMIT <= S * M * nxt * 4
+    assert X.c_fits_wt(M, N, nxt, 4)        # the slice loop's launches are write-through ones
+    rows = X.GATE_SCALED[0]                                          # gate 4: fp8 and fp4 scales
+    for al in (4, 8):
+        last, nxt = X.gate_ld(lambda ld: X.scale_rows_ok(rows, ld), al)
+        assert nxt == last + al and rows * last < 2 ** 31 <= rows * nxt
+    assert X.pt4_ld_ok(X.PT4_LD_BYTES // 2, 2) and not X.pt4_ld_ok(X.PT4_LD_BYTES // 2 + 8, 2)
+    assert X.gate_ld(lambda ld: X.pt4_ld_ok(ld, 4), 4) == (2 ** 20, 2 ** 20 + 4)
+
+
+def test_fill_word():
+    assert X.fill_word(SENTINEL, torch.uint8) == -0x0606060606060607        # bytes 0xF9
+    assert X.fill_word(POISON, torch.uint8) == 0x0505050505050505
+    assert X.fill_word(SENTINEL, torch.float32) == int.from_bytes(
+        torch.tensor([SENTINEL, SENTINEL]).view(torch.uint8).numpy().tobytes(), "little",
+        signed=True)
+    for dtype in (torch.bfloat16, torch.float16, FP8, torch.float32, torch.float64):
+        w = torch.tensor([X.fill_word(POISON, dtype)], dtype=torch.int64).view(dtype)
+        assert bool((w.to(torch.float64) == POISON).all())
