@@ -161,7 +161,7 @@ PYBIND11_MODULE(_C, m) {
            int N, int K, int din, int dout, int tile, int mode, int64_t a_grp, int64_t a_gstride,
            int64_t c_grp, int64_t c_gstride, uintptr_t stream, int act, int ksplit,
            uintptr_t a_scale, uintptr_t b_scale, int64_t a_scale_ld, int64_t b_scale_ld,
-           uintptr_t c_scale, int64_t c_scale_ld) {
+           uintptr_t c_scale, int64_t c_scale_ld, int glu) {
           GemmArgs g = make_args(a, b, c, lda, ldb, ldc, M, N, K, a_grp, a_gstride, c_grp,
                                  c_gstride);
           g.act = act;
@@ -172,6 +172,7 @@ PYBIND11_MODULE(_C, m) {
           g.b_scale_ld = b_scale_ld;
           g.c_scale = (uint8_t*)c_scale;
           g.c_scale_ld = c_scale_ld;
+          g.glu = glu != 0;
           check(gemm_launch(g, din, dout, tile, mode, (hipStream_t)stream), "gemm_launch");
         },
         py::arg("a"), py::arg("b"), py::arg("c"), py::arg("lda"), py::arg("ldb"), py::arg("ldc"),
@@ -180,7 +181,7 @@ PYBIND11_MODULE(_C, m) {
         py::arg("c_grp") = 0, py::arg("c_gstride") = 0, py::arg("stream") = 0,
         py::arg("act") = 0, py::arg("ksplit") = 1, py::arg("a_scale") = 0,
         py::arg("b_scale") = 0, py::arg("a_scale_ld") = 0, py::arg("b_scale_ld") = 0,
-        py::arg("c_scale") = 0, py::arg("c_scale_ld") = 0);
+        py::arg("c_scale") = 0, py::arg("c_scale_ld") = 0, py::arg("glu") = 0);
   // x[R, K] f32 / f16 / bf16 -> q[R, K] e4m3 + s[R, K / 32] E8M0 bytes; mxfp4_quantize: the same
   // -> q[R, K / 2] E2M1 nibble pairs (ldq in bytes) + s
   def_row_quantizer(m, "mx_quantize", mx_quantize_launch);

@@ -190,6 +190,13 @@ struct GemmArgs {
   // apart: the layout the next GEMM reads as its A and a_scale. Plain C rows only.
   uint8_t* c_scale = nullptr;
   int64_t c_scale_ld = 0;
+  // Gated (GLU) epilogue (optional; the tiled kernel, codes of mxs_offers()): b is [N, K] with
+  // gate and up rows interleaved in groups of 32 (rows 64g .. 64g + 31 gate, 64g + 32 .. 64g + 63
+  // the matching up rows) and c has N / 2 columns, c[i, 32g + j] = act(acc[i, 64g + j]) *
+  // acc[i, 64g + 32 + j] in f32, then rounded to dout or quantised (c_scale: [M, N / 64]). N stays
+  // the number of b rows; N % 64 == 0 (whole blocks as the reader takes them for a quantised
+  // output: N % 256, fp4 N % 512); ldc >= N / 2. Plain rows only.
+  int glu = 0;
 };
 // The byte view of a launch whose operands and / or output are fp4: the kernels address bytes (two
 // E2M1 elements each), so K, lda and ldb of fp4 operands and ldc of an fp4 output are halved.

@@ -148,6 +148,12 @@ template <class Mma> struct is_pair<Mma, std::void_t<decltype(Mma::kPair)>>
 template <class Mma, class = void> struct is_scaled : std::false_type {};
 template <class Mma> struct is_scaled<Mma, std::void_t<decltype(Mma::kScaled)>>
     : std::integral_constant<bool, Mma::kScaled> {};
+// Flavours whose tiled kernel has gated (GLU) instantiations: the operands gemm_launch takes
+// with GemmArgs::glu (bf16, f16, block-scaled fp8 / fp4).
+template <class Mma> struct has_glu
+    : std::integral_constant<bool, std::is_same<Mma, MmaBF16>::value ||
+                                       std::is_same<Mma, MmaF16>::value ||
+                                       is_scaled<Mma>::value> {};
 
 // Compile-time emission of the {PER x MFMA, 1 x VMEM, n_g x DS_READ} interleave pattern
 // (sched_group_barrier arguments must be literal constants).
@@ -394,7 +400,7 @@ __device__ __forceinline__ void wait_tile(const GemmArgs& p, int64_t m0, int BM)
 // Any shape on the fast path (ragged edges: clamped row loads, guarded stores). With MmaMX the
 // compute step is one v_mfma_scale_f32_16x16x128_f8f6f4 per 128-byte K-row (unit E8M0 scales =
 // 127): 2x the bf16 MFMA rate (MI355X_MICROARCH.md "Matrix cores"), same staging.
-template <class Mma, int OUT, int BM, int BN, int WM, int WN, bool ILV = false>
+template <class Mma, int OUT, int BM, int BN, int WM, int WN, bool ILV = false, bool GLU = false>
 __global__ __launch_bounds__(WM* WN * 64) void gemm_tn_kernel(const GemmArgs p) {
   constexpr int NT = WM * WN * 64, NW = WM * WN;
   constexpr int ROWB = 128;  // bytes per row per K-tile
@@ -674,6 +680,11 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_tn_kernel(const GemmArgs p) 
   compute(cur);
 
   // Epilogue: lane holds C[row = .. + frow][col = .. + 4*fq + r], r = 0..3.
+  // GLU: the gated form (GemmArgs::glu), instantiations of their own for a wave's 64 columns
+  // (NR = 4: every code of mxs_offers()). As a run-time branch in the ungated kernels it cost the
+  // bf16 quantising flavour 1.1 - 1.4 % (docs/RESULTS.md) and the NR = 8 forms 36 - 80 bytes of
+  // scratch, so it is a template argument and the ungated instantiations hold none of it.
+  static_assert(!GLU || (NR == 4 && !ILV && has_glu<Mma>::value), "gated: 64 columns per wave");
   if constexpr (OUT == DT_FP8 || OUT == DT_FP4) {
     // Quantising epilogue (GemmArgs::c_scale): one MX block is 32 consecutive columns of a C row,
     // i.e. fragments j = 2b, 2b + 1 of the four lanes frow + 16 g: 8 values per lane, then a max
@@ -690,11 +701,9 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_tn_kernel(const GemmArgs p) 
       const int64_t rc = rok ? row : p.M - 1;
       char* crow = (char*)p.c + rc * p.ldc;
       uint8_t* srow = p.c_scale + rc * p.c_scale_ld;
-#pragma unroll
-      for (int b = 0; b < NR / 2; ++b) {
-        const int64_t col = n0 + wn * TN + b * 32;  // the block's first column
-        const bool ok = rok && col < p.N;
-        const f32x4 v0 = act4(acc[i][2 * b], p.act), v1 = act4(acc[i][2 * b + 1], p.act);
+      // one block: the lane's 8 values, the block's first output column, whether it is stored
+      auto block = [&](const f32x4 v0, const f32x4 v1, const int64_t col, const bool ok)
+                       __attribute__((always_inline)) {
         const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
         unsigned m = 0;
 #pragma unroll
@@ -728,6 +737,24 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_tn_kernel(const GemmArgs p) 
           }
         }
         if (ok && fq == 0) srow[col / 32] = (uint8_t)(e + 127);
+      };
+      if constexpr (GLU) {
+        // Gated: a wave's 64 columns are 32 gate and the 32 matching up columns, fragments 4b,
+        // 4b + 1 against 4b + 2, 4b + 3 of the same lane, so act(gate) * up is a lane-local f32
+        // multiply and its 32 results are one block of the N / 2 output columns.
+#pragma unroll
+        for (int b = 0; b < NR / 4; ++b) {
+          const int64_t col = (n0 + wn * TN) / 2 + b * 32;
+          block(act4(acc[i][4 * b], p.act) * acc[i][4 * b + 2],
+                act4(acc[i][4 * b + 1], p.act) * acc[i][4 * b + 3], col, rok && 2 * col < p.N);
+        }
+      } else {
+#pragma unroll
+        for (int b = 0; b < NR / 2; ++b) {
+          const int64_t col = n0 + wn * TN + b * 32;  // the block's first column
+          block(act4(acc[i][2 * b], p.act), act4(acc[i][2 * b + 1], p.act), col,
+                rok && col < p.N);
+        }
       }
     }
   } else {
@@ -737,6 +764,21 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_tn_kernel(const GemmArgs p) 
       const int64_t row = m0 + wm * TM + i * 16 + frow;
       if (row >= p.M) continue;
       char* crow = c_row<OSZ>(p, row);
+      if constexpr (GLU) {
+        // Gated: fragments 4b + h (gate) and 4b + 2 + h (up) give 4 of the N / 2 output columns;
+        // N % 64 == 0, so a 64-column group is wholly inside or outside and there is no tail.
+#pragma unroll
+        for (int b = 0; b < NR / 4; ++b) {
+          if (n0 + wn * TN + b * 64 >= p.N) continue;
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const int64_t col = (n0 + wn * TN) / 2 + b * 32 + h * 16 + fq * 4;
+            Store4<OUT>::st(crow + col * OSZ,
+                            act4(acc[i][4 * b + h], p.act) * acc[i][4 * b + 2 + h]);
+          }
+        }
+        continue;
+      }
 #pragma unroll
       for (int j = 0; j < NR; ++j) {
         const int64_t col = n0 + wn * TN + j * 16 + fq * 4;
@@ -2114,7 +2156,8 @@ constexpr bool offers_every_tile(int) { return true; }
 // 256x256 one, which takes what they do not; the MX kernels are never interleaved, and no code
 // that mxs_offers() / mx4_offers() list is: gemm.h). The one launch site of gemm_tn_kernel:
 // Offers is every code, or the codes a block-scaled / quantising flavour is built for; a code it
-// does not list answers hipErrorNotSupported and instantiates nothing. fp4 operands and an fp4
+// does not list answers hipErrorNotSupported and instantiates nothing (a gated launch, GemmArgs::
+// glu, answers hipErrorInvalidValue for every code without a gated kernel). fp4 operands and an fp4
 // output are addressed in bytes: GemmArgs arrive in elements, the byte view is formed here.
 // hipErrorInvalidValue for a code without a kernel (5, 8, 9, 13-15: retired kernel families).
 template <class Mma, int OUT, bool (*Offers)(int) = offers_every_tile>
@@ -2124,12 +2167,21 @@ hipError_t launch_tiled(const GemmArgs& p_in, int tile, hipStream_t s) {
     return dispatch_int<kNumTileCfgs>(tile_slot(tile), [&](auto slot) {
       constexpr TileCfg c = kTileCfgs[decltype(slot)::value];
       if constexpr (!Offers(c.code)) {
-        return hipErrorNotSupported;
+        return p.glu ? hipErrorInvalidValue : hipErrorNotSupported;
       } else {
         constexpr bool ILV = c.ilv && !is_pair<Mma>::value;
         const int tiles = ((p.M + c.rows - 1) / c.rows) * ((p.N + c.cols - 1) / c.cols);
-        hipLaunchKernelGGL((gemm_tn_kernel<Mma, OUT, c.rows, c.cols, c.wm, c.wn, ILV>),
-                           dim3(tiles), dim3(c.wm * c.wn * 64), 0, s, p);
+        if (p.glu) {  // the gated instantiations: the codes of mxs_offers(), 64 columns per wave
+          if constexpr (has_glu<Mma>::value && mxs_offers(c.code) && c.cols / c.wn == 64 && !ILV) {
+            hipLaunchKernelGGL((gemm_tn_kernel<Mma, OUT, c.rows, c.cols, c.wm, c.wn, ILV, true>),
+                               dim3(tiles), dim3(c.wm * c.wn * 64), 0, s, p);
+          } else {
+            return hipErrorInvalidValue;  // (as every refusal of a gated launch: gemm.h)
+          }
+        } else {
+          hipLaunchKernelGGL((gemm_tn_kernel<Mma, OUT, c.rows, c.cols, c.wm, c.wn, ILV>),
+                             dim3(tiles), dim3(c.wm * c.wn * 64), 0, s, p);
+        }
         return hipGetLastError();
       }
     });
@@ -2269,6 +2321,11 @@ hipError_t launch_pt8(const GemmArgs& p, hipStream_t s) {
 
 template <class Mma, int OUT>
 hipError_t launch_cfg(const GemmArgs& p, int tile, hipStream_t s) {
+  // a gated (GLU) epilogue lives in the tiled kernel only, for the codes mxs_offers() lists
+  if (p.glu) {
+    if constexpr (has_glu<Mma>::value) return launch_tiled<Mma, OUT, mxs_offers>(p, tile, s);
+    else return hipErrorInvalidValue;
+  }
   // whole 256x256 tiles: the ping-pong kernels. pt8 is persistent: no arrival flags (a block's
   // tiles are fixed up front)
   if (tile == TILE_PT8 && t8_ok(p) && p.flags == nullptr) return launch_pt8<Mma, OUT>(p, s);
@@ -2283,6 +2340,7 @@ hipError_t launch_cfg(const GemmArgs& p, int tile, hipStream_t s) {
 }
 template <int OUT>
 hipError_t launch_mx_cfg(const GemmArgs& p, int tile, hipStream_t s) {
+  if (p.glu) return hipErrorInvalidValue;  // (unit scales: no gated epilogue, see has_glu)
   // whole 256x256 tiles: the ping-pong schedules (persistent with >= 2 tiles per CU)
   if (tile == TILE_PT4 && pt4_ok(p, 1) && !(p.c_table && (p.a_table || p.a_grp != p.M)))
     return launch_pt4<MmaMX, OUT>(p, s);

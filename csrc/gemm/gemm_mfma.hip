@@ -174,6 +174,56 @@ static hipError_t gemm_launch_qout(const GemmArgs& p, int din, int dout, int til
   return q4 ? launch_qout_fp4(p, din, tile, s) : launch_qout_fp8(p, din, tile, s);
 }
 
+// Gated (GLU) epilogue (GemmArgs::glu): the tiled kernel's offered codes, bf16 / f16 / block-scaled
+// fp8 / block-scaled fp4 operands, a dense output the operands pair with or a quantised one, plain
+// rows; or hipErrorInvalidValue, never a launch of something else. N counts the rows of b; the
+// output, its scales and every bound on them have N / 2 columns.
+static hipError_t gemm_launch_glu(const GemmArgs& p, int din, int dout, int tile, int mode,
+                                  hipStream_t s) {
+  const bool in4 = din == DT_FP4, scaled = din == DT_FP8 || in4;
+  const bool q4 = dout == DT_FP4, qout = dout == DT_FP8 || q4;
+  if (din != DT_BF16 && din != DT_F16 && !scaled) return hipErrorInvalidValue;
+  // fp8 / fp4 operands: block-scaled only (both scales); 16-bit operands carry none
+  if (scaled ? (p.a_scale == nullptr || p.b_scale == nullptr)
+             : (p.a_scale != nullptr || p.b_scale != nullptr))
+    return hipErrorInvalidValue;
+  if (qout != (p.c_scale != nullptr)) return hipErrorInvalidValue;
+  if (!qout && dout != DT_F32 && !(scaled ? dout == DT_BF16 || dout == DT_F16 : dout == din))
+    return hipErrorInvalidValue;
+  if (mode == GEMM_MODE_GENERIC || mode < GEMM_MODE_AUTO || mode > GEMM_MODE_MX ||
+      (!scaled && mode == GEMM_MODE_MX))
+    return hipErrorInvalidValue;
+  if (tile != TILE_AUTO && !mxs_offers(tile)) return hipErrorInvalidValue;
+  // whole 64-row gate / up groups; N / 2 in whole blocks as the GEMM that reads them takes them
+  if (p.M < 0 || p.N < 0 || p.K <= 0 || p.N % (q4 ? 512 : qout ? 256 : 64))
+    return hipErrorInvalidValue;
+  const hipError_t e = plain_operands_only(p, true, true, hipErrorInvalidValue);
+  if (e != hipSuccess) return e;
+  if (p.M == 0 || p.N == 0) return hipSuccess;
+  if (in4 && (p.K % 256 || p.lda % 2 || p.ldb % 2)) return hipErrorInvalidValue;
+  if (q4 && p.ldc % 2) return hipErrorInvalidValue;
+  const GemmArgs q = fp4_byte_view(p, in4, q4);
+  if (p.a == nullptr || p.b == nullptr || p.c == nullptr || p.lda < p.K || p.ldb < p.K ||
+      p.ldc < p.N / 2 || !gemm_fast_path_ok(q, in4 ? DT_U8 : din, qout ? DT_U8 : dout))
+    return hipErrorInvalidValue;
+  if (scaled && !scale_operands_ok(p, in4 ? 8 : 4)) return hipErrorInvalidValue;
+  if (qout) {  // rows and scales as gemm_launch_qout asks for them, N / 64 scale bytes per row
+    const int cal = q4 ? 8 : 4;
+    if (q.ldc % 16 || ((uintptr_t)p.c & 15) || ((uintptr_t)p.c_scale & (cal - 1)) ||
+        p.c_scale_ld % cal || p.c_scale_ld < p.N / 64 ||
+        (int64_t)p.M * p.c_scale_ld >= (int64_t(1) << 31))
+      return hipErrorInvalidValue;
+  }
+  if (tile == TILE_AUTO) tile = mxs_tile_for(choose_tile(p.M, p.N, p.K, din));
+  if (tile < 0) return hipErrorInvalidValue;
+  GemmArgs g = p;
+  g.glu = 1;
+  if (qout) return q4 ? launch_qout_fp4(g, din, tile, s) : launch_qout_fp8(g, din, tile, s);
+  if (in4) return launch_fast_mx4(g, dout, tile, s);
+  if (scaled) return launch_fast_mxs(g, dout, tile, s);
+  return launch_fast(g, din, dout, tile, s);
+}
+
 hipError_t gemm_launch(const GemmArgs& p_in, int din, int dout, int tile, int mode,
                        hipStream_t s) {
   GemmArgs p = p_in;
@@ -181,6 +231,7 @@ hipError_t gemm_launch(const GemmArgs& p_in, int din, int dout, int tile, int mo
   if (p.c_grp <= 0) { p.c_grp = p.M > 0 ? p.M : 1; p.c_gstride = p.c_grp; }
   // known codes only (the retired families' codes are refused, not rerouted)
   if (tile != TILE_AUTO && tile_slot(tile) < 0) return hipErrorInvalidValue;
+  if (p.glu) return gemm_launch_glu(p, din, dout, tile, mode, s);
   // quantised output: dout fp8 / fp4 and output scales go together
   if (dout == DT_FP8 || dout == DT_FP4) return gemm_launch_qout(p, din, dout, tile, mode, s);
   if (p.c_scale != nullptr) return hipErrorInvalidValue;

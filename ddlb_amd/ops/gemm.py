@@ -13,6 +13,8 @@ scales with ``a_scale`` / ``w_scale``, see :mod:`ddlb_amd.ops.mx`), float4_e2m1f
 (MXFP4: E2M1 pairs, always with block scales, at 2x the MX-fp8 rate), f64 (generic kernel).
 ``out_quant="mx" | "mxfp4"``: bf16 / f16 / block-scaled fp8 / block-scaled fp4 -> MX-fp8 or MXFP4
 data and E8M0 scales per 32 output columns, quantised in the GEMM's epilogue.
+``glu=True``: the same operands, ``w`` holding interleaved gate and up rows (``pack_glu``); the
+epilogue writes ``act(gate) * up``, half as many columns, dense or quantised.
 """
 
 from __future__ import annotations
@@ -234,8 +236,6 @@ def _check_out_quant(a, w, out_quant, out=None, out_scale=None, *, a_scale=None,
     import torch
     from types import SimpleNamespace
 
-    from ddlb_amd.ops.mx import check_quant_pair_layout, check_quant_pair_types
-
     if out_quant not in OUT_QUANTS:
         raise ValueError(f"out_quant must be None or one of {OUT_QUANTS}, not {out_quant!r}")
     q4 = out_quant == "mxfp4"
@@ -292,43 +292,58 @@ def _check_out_quant(a, w, out_quant, out=None, out_scale=None, *, a_scale=None,
                         f"{a.dtype}")
     if M >= 2 ** 31 or N >= 2 ** 31 or K >= 2 ** 31:
         raise ValueError("dimensions must fit in 32 bits")
-    ncol, sal = (N // 2 if q4 else N), (8 if q4 else 4)
+    _check_quant_outputs(a, out, out_scale, out_quant, M, N)
+    return M, N, K
+
+
+def _check_quant_outputs(a, out, out_scale, out_quant, M, cols):
+    """``out`` / ``out_scale`` of a quantised output of ``cols`` columns (``N``; ``N / 2`` with
+    ``glu``), where given: types, device, shape, layout, and the scales' 2 GiB span."""
+    from ddlb_amd.ops.mx import check_quant_pair_layout, check_quant_pair_types
+
+    q4 = out_quant == "mxfp4"
+    qdt = out_quant_dtype(out_quant)
+    ncol, sal = (cols // 2 if q4 else cols), (8 if q4 else 4)
     check_quant_pair_types(("out", "out_scale"), out, out_scale, qdt, f"out_quant={out_quant!r}")
-    for name, t, cols in (("out", out, ncol), ("out_scale", out_scale, N // 32)):
+    for name, t, tc in (("out", out, ncol), ("out_scale", out_scale, cols // 32)):
         if t is None:
             continue
         if t.device != a.device:
             raise ValueError(f"{name} is on {t.device}, the operands on {a.device}")
-        if t.dim() != 2 or t.shape[0] < M or t.shape[1] != cols:
-            raise ValueError(f"{name} must have shape (>= {M}, {cols}), not {tuple(t.shape)}")
-    check_quant_pair_layout(("out", "out_scale"), out, out_scale, ncol, N // 32, sal)
+        if t.dim() != 2 or t.shape[0] < M or t.shape[1] != tc:
+            raise ValueError(f"{name} must have shape (>= {M}, {tc}), not {tuple(t.shape)}")
+    check_quant_pair_layout(("out", "out_scale"), out, out_scale, ncol, cols // 32, sal)
     if out_scale is not None and M * out_scale.stride(0) >= 2 ** 31:
         raise ValueError("out_scale spans 2 GiB or more")
-    if M * (N // 32) >= 2 ** 31:
+    if M * (cols // 32) >= 2 ** 31:
         raise ValueError("out_scale spans 2 GiB or more")
-    return M, N, K
 
 
 def _launch(C, a, w, c, M, N, K, tile, mode, s, *, a_grp=0, a_gstride=0, c_grp=0, c_gstride=0,
-            act=0, ksplit=None, a_scale=None, w_scale=None, out_scale=None):
+            act=0, ksplit=None, a_scale=None, w_scale=None, out_scale=None, glu=False):
     """The one call of ``C.gemm``: pointers, leading dimensions and dtype codes from the tensors
     (fp4 data: two elements per stored byte, dimensions go in ELEMENTS), then the optional tail
     in the extension's positional order: ``ksplit``, the four operand-scale arguments (block
-    scales always run ``mode="mx"``), the two output-scale arguments."""
+    scales always run ``mode="mx"``), the two output-scale arguments, ``glu`` (the whole tail
+    then, zeros for what is absent)."""
     am, cm = (2 if _is_fp4(a) else 1), (2 if _is_fp4(c) else 1)
     scaled = a_scale is not None
     args = [a.data_ptr(), w.data_ptr(), c.data_ptr(), am * a.stride(0), am * w.stride(0),
             cm * c.stride(0), M, N, K, DT_FP4 if am == 2 else dtype_code(a.dtype),
             DT_FP4 if cm == 2 else dtype_code(c.dtype), TILES[tile],
             MODES["mx"] if scaled else MODES[mode], a_grp, a_gstride, c_grp, c_gstride, s, act]
-    if ksplit is not None or scaled or out_scale is not None:
+    if ksplit is not None or scaled or out_scale is not None or glu:
         args.append(1 if ksplit is None else ksplit)
     if scaled:
         args += [a_scale.data_ptr(), w_scale.data_ptr(), a_scale.stride(0), w_scale.stride(0)]
-    elif out_scale is not None:
+    elif out_scale is not None or glu:
         args += [0, 0, 0, 0]
     if out_scale is not None:
         args += [out_scale.data_ptr(), out_scale.stride(0)]
+    elif glu:
+        args += [0, 0]
+    if glu:
+        args.append(1)
     C.gemm(*args)
 
 
@@ -371,10 +386,194 @@ def _gemm_out_quant(a, w, out, out_scale, out_quant, *, out_dtype, tile, mode, M
     return out[:M], out_scale[:M]
 
 
+GLU_GROUP = 32  # gate / up rows alternate in groups of one MX block (GemmArgs::glu)
+
+
+def _as_bytes(t):
+    """One-byte dtypes (fp8, fp4 pairs) as uint8, which torch stacks and reshapes everywhere."""
+    import torch
+
+    return t.view(torch.uint8) if t.element_size() == 1 and t.dtype != torch.uint8 else t
+
+
+def pack_glu(gate, up):
+    """``[F, K]`` gate and up rows -> the ``[2F, K]`` weight ``gemm(glu=True)`` reads: rows
+    ``64g .. 64g + 31`` are gate rows ``32g .. 32g + 31``, rows ``64g + 32 .. 64g + 63`` the
+    matching up rows. Any dtype: quantised data and their ``uint8`` scales pack row by row (a
+    row-wise quantisation commutes with a row permutation). ``F % 32 == 0``."""
+    import torch
+
+    if gate.dim() != 2 or up.dim() != 2 or gate.shape != up.shape or gate.dtype != up.dtype:
+        raise ValueError(f"pack_glu takes two 2-D tensors of one shape and dtype, not "
+                         f"{tuple(gate.shape)} {gate.dtype} and {tuple(up.shape)} {up.dtype}")
+    F, K = gate.shape
+    if F % GLU_GROUP:
+        raise ValueError(f"pack_glu needs F % {GLU_GROUP} == 0 (F = {F})")
+    g, u = (_as_bytes(t).reshape(F // GLU_GROUP, GLU_GROUP, K) for t in (gate, up))
+    return torch.stack((g, u), dim=1).reshape(2 * F, K).view(gate.dtype)
+
+
+def unpack_glu(w):
+    """The inverse of :func:`pack_glu`: ``[2F, K]`` -> ``(gate, up)``, ``[F, K]`` each."""
+    if w.dim() != 2 or w.shape[0] % (2 * GLU_GROUP):
+        raise ValueError(f"unpack_glu takes a 2-D tensor of a multiple of {2 * GLU_GROUP} rows, "
+                         f"not {tuple(w.shape)}")
+    N, K = w.shape
+    v = _as_bytes(w).reshape(N // (2 * GLU_GROUP), 2, GLU_GROUP, K)
+    return tuple(v[:, h].reshape(N // 2, K).view(w.dtype) for h in (0, 1))
+
+
+def glu_reference(c, act: str = "none"):
+    """The specification of the gated epilogue on an f32 ``[M, 2F]`` product ``c = a @ w.T`` (any
+    device): ``out[i, 32g + j] = act(c[i, 64g + j]) * c[i, 64g + 32 + j]``, f32 ``[M, F]``."""
+    import torch
+
+    from ddlb_amd.parallel.sim import apply_act
+
+    if act not in ACTS:
+        raise ValueError(f"unknown activation {act!r}")
+    if c.dim() != 2 or c.shape[1] % (2 * GLU_GROUP) or c.dtype != torch.float32:
+        raise ValueError(f"glu_reference takes an f32 [M, 2F] product with 2F % "
+                         f"{2 * GLU_GROUP} == 0, not {tuple(c.shape)} {c.dtype}")
+    M, N = c.shape
+    v = c.reshape(M, N // (2 * GLU_GROUP), 2, GLU_GROUP)
+    return (apply_act(v[:, :, 0], ACTS[act]) * v[:, :, 1]).reshape(M, N // 2)
+
+
+def _check_glu(a, w, out=None, out_scale=None, *, out_quant=None, out_dtype=None, a_scale=None,
+               w_scale=None, tile: str = "auto", mode: str = "auto", M: Optional[int] = None,
+               a_grp: int = 0, c_grp: int = 0, ksplit: int = 0, act: str = "none"):
+    """Every refusal of the gated GEMM (``glu=True``), on the host and before anything is loaded
+    or launched (CPU tensors pass through it). ``out`` / ``out_scale`` are checked when given.
+    Returns ``(M, N, K, output dtype)``: ``N`` the rows of ``w``; the output has ``N / 2``
+    columns."""
+    import torch
+    from types import SimpleNamespace
+
+    if act not in ACTS:
+        raise ValueError(f"unknown activation {act!r}")
+    if out_quant is not None and out_quant not in OUT_QUANTS:
+        raise ValueError(f"out_quant must be None or one of {OUT_QUANTS}, not {out_quant!r}")
+    q4 = out_quant == "mxfp4"
+    if q4 and _fp4_dtype() is None:
+        raise TypeError("out_quant='mxfp4' needs torch.float4_e2m1fn_x2")
+    if out_quant is None and out_scale is not None:
+        raise ValueError("out_scale goes with out_quant")
+    if a.dim() != 2 or w.dim() != 2:
+        raise ValueError("native GEMM expects 2-D operands")
+    fp4 = _is_fp4(a) or _is_fp4(w)
+    M = a.shape[0] if M is None else int(M)
+    N = w.shape[0]
+    K = 2 * a.shape[1] if fp4 else a.shape[1]
+    if a.shape[1] != w.shape[1]:
+        raise ValueError(f"K mismatch: A {tuple(a.shape)} vs W {tuple(w.shape)}")
+    if not 0 <= M <= a.shape[0]:
+        raise ValueError(f"M = {M} is outside A's {a.shape[0]} rows")
+    nmod = 512 if q4 else 256 if out_quant else 2 * GLU_GROUP
+    if N % nmod:
+        why = ("N / 2 in whole 32-column blocks, as many as the GEMM that reads them takes per "
+               "K-tile" if out_quant else "whole groups of 32 gate and 32 up rows")
+        raise ValueError(f"glu with out_quant={out_quant!r} needs N % {nmod} == 0 (N = {N}): {why}")
+    if mode == "generic":
+        raise ValueError("a gated epilogue comes from the tiled MFMA kernel, not mode='generic'")
+    if mode not in MODES:
+        raise ValueError(f"unknown mode {mode!r}")
+    if tile != "auto" and tile not in SCALED_TILES:
+        raise ValueError(f"a gated epilogue is offered for tile auto / {SCALED_TILES}, not "
+                         f"{tile!r} (the ping-pong, interleaved and 256x256 kernels have none)")
+    if int(ksplit) > 1:
+        raise ValueError("a gated epilogue does not combine with a K-split")
+    if a_grp not in (0, M) or c_grp not in (0, M):
+        raise ValueError("a gated epilogue needs plain A and C rows (no grouped rows)")
+    # the inputs: bf16, f16, block-scaled fp8, block-scaled fp4; the dense outputs they pair with
+    if fp4:
+        _check_fp4(a, w, SimpleNamespace(dtype=torch.bfloat16), a_scale, w_scale, M, tile, mode,
+                   a_grp, int(ksplit))
+        dense = (torch.bfloat16, torch.float16, torch.float32)
+    elif a.dtype == torch.float8_e4m3fn or w.dtype == torch.float8_e4m3fn:
+        if a.dtype != w.dtype:
+            raise TypeError(f"A dtype {a.dtype} != W dtype {w.dtype}")
+        if a_scale is None or w_scale is None:
+            raise ValueError("a gated epilogue on fp8 operands needs a_scale and w_scale "
+                             "(the unit-scale kernels have none)")
+        _check_scales(a, w, a_scale, w_scale, M, tile, mode, a_grp, int(ksplit))
+        dense = (torch.bfloat16, torch.float16, torch.float32)
+    elif a.dtype in (torch.bfloat16, torch.float16):
+        if a.dtype != w.dtype:
+            raise TypeError(f"A dtype {a.dtype} != W dtype {w.dtype}")
+        if a_scale is not None or w_scale is not None:
+            raise TypeError(f"block scales need fp8 / fp4 operands, not {a.dtype}")
+        if mode == "mx":
+            raise ValueError(f"mode='mx' needs fp8 / fp4 operands, not {a.dtype}")
+        dense = (a.dtype, torch.float32)
+    else:
+        raise TypeError(f"glu takes bf16, f16, scaled fp8 or scaled fp4 operands, not {a.dtype}")
+    if M >= 2 ** 31 or N >= 2 ** 31 or K >= 2 ** 31:
+        raise ValueError("dimensions must fit in 32 bits")
+    if out_quant is not None:
+        qdt = out_quant_dtype(out_quant)
+        if out_dtype is not None and out_dtype != qdt:
+            raise TypeError(f"out_quant={out_quant!r} writes {qdt}, not out_dtype={out_dtype}")
+        _check_quant_outputs(a, out, out_scale, out_quant, M, N // 2)
+        return M, N, K, qdt
+    odt = out.dtype if out is not None else (out_dtype or dense[0])
+    if out is not None and out_dtype is not None and out_dtype != out.dtype:
+        raise TypeError(f"out is {out.dtype}, out_dtype={out_dtype}")
+    if odt not in dense:
+        raise TypeError(f"a gated epilogue on {a.dtype} operands writes one of {dense}, not {odt}")
+    if out is not None:
+        if out.device != a.device:
+            raise ValueError(f"out is on {out.device}, the operands on {a.device}")
+        if out.dim() != 2 or out.shape[0] < M or out.shape[1] != N // 2:
+            raise ValueError(f"out must have shape (>= {M}, {N // 2}), not {tuple(out.shape)}")
+        if out.stride(1) != 1 or out.stride(0) < N // 2:
+            raise ValueError(f"out needs unit inner stride and a row stride of at least "
+                             f"{N // 2} (strides {tuple(out.stride())})")
+    return M, N, K, odt
+
+
+def _gemm_glu(a, w, out, out_scale, *, out_quant, out_dtype, tile, mode, M, a_grp, c_grp, stream,
+              act, ksplit, a_scale, w_scale):
+    """The gated launch: ``act(gate) * up`` out of the tiled kernel's epilogue, ``[M, N / 2]``
+    dense or as ``(q, s)``. Every refusal comes first, before the extension is loaded."""
+    import torch
+
+    M, N, K, odt = _check_glu(a, w, out, out_scale, out_quant=out_quant, out_dtype=out_dtype,
+                              a_scale=a_scale, w_scale=w_scale, tile=tile, mode=mode, M=M,
+                              a_grp=a_grp, c_grp=c_grp, ksplit=ksplit, act=act)
+    C = load()
+    fp4, q4 = _is_fp4(a), out_quant == "mxfp4"
+    _check_placement(a, w)
+    if out is None and out_quant is not None:
+        out = torch.empty((M, N // 4 if q4 else N // 2), dtype=torch.uint8,
+                          device=a.device).view(odt)
+    elif out is None:
+        out = torch.empty((M, N // 2), dtype=odt, device=a.device)
+    if out_quant is not None and out_scale is None:
+        out_scale = torch.empty((M, N // 64), dtype=torch.uint8, device=a.device)
+    kb = K // 2 if fp4 else K  # the operands as the byte / element matrices the kernel reads
+    if M and N and not C.gemm_fast_path_ok(a.data_ptr(), w.data_ptr(), out.data_ptr(),
+                                           a.stride(0), w.stride(0), out.stride(0), M, N, kb,
+                                           DT_U8 if fp4 else dtype_code(a.dtype),
+                                           DT_U8 if out_quant else dtype_code(odt)):
+        raise ValueError("a gated epilogue needs the MFMA fast path: 16-byte-aligned operand "
+                         "rows, 8-byte-aligned output rows and K a whole number of 128-byte "
+                         "K-tiles")
+    s = stream if stream is not None else torch.cuda.current_stream(a.device).cuda_stream
+    _launch(C, a, w, out, M, N, K, tile, mode, s, act=ACTS[act], a_scale=a_scale,
+            w_scale=w_scale, out_scale=out_scale, glu=True)
+    if stream is not None:  # the outputs stay allocated until that stream reaches them
+        out.record_stream(torch.cuda.ExternalStream(s))
+        if out_scale is not None:
+            out_scale.record_stream(torch.cuda.ExternalStream(s))
+    return out if out_quant is None else (out[:M], out_scale[:M])
+
+
 def gemm(a, w, out=None, *, out_dtype=None, tile: str = "auto", mode: str = "auto",
          M: Optional[int] = None, a_grp: int = 0, a_gstride: int = 0, c_grp: int = 0,
          c_gstride: int = 0, stream=None, act: str = "none", ksplit: int = 0,
-         a_scale=None, w_scale=None, out_quant: Optional[str] = None, out_scale=None):
+         a_scale=None, w_scale=None, out_quant: Optional[str] = None, out_scale=None,
+         glu: bool = False):
     """``out[:M] = act(a[:M] @ w.T)`` on the current HIP stream (grouped-row addressing and a
     fused epilogue activation — none / gelu (tanh) / relu / silu — optional). ``ksplit``: 0 =
     auto (:func:`split_k_factor` for plain-row auto-tile GEMMs with no activation and a dense
@@ -399,9 +598,22 @@ def gemm(a, w, out=None, *, out_dtype=None, tile: str = "auto", mode: str = "aut
     ``float4_e2m1fn_x2 [M, N / 2]`` and ``uint8 [M, N / 32]``, laid out so that they go straight
     back in as ``a`` and ``a_scale``. ``out`` / ``out_scale`` may be preallocated (16-byte-aligned
     data rows, a scale row stride that is a multiple of 4, 8 for fp4). :func:`_check_out_quant`
-    holds every refusal."""
+    holds every refusal.
+
+    ``glu=True`` (SwiGLU / GeGLU / ReGLU / bilinear by ``act``): ``w`` is ``[2F, K]`` with gate
+    and up rows interleaved in groups of 32 (:func:`pack_glu`) and the epilogue multiplies
+    ``act(gate)`` by ``up`` in f32, so the result has ``F = N / 2`` columns
+    (:func:`glu_reference`): dense (``N % 64 == 0``), or with ``out_quant`` as ``(q, s)`` of
+    ``N / 2`` columns and ``N / 64`` scales per row (``N % 256``, fp4 ``N % 512 == 0``). Same
+    operands, tiles and plain rows as ``out_quant`` (``a_grp`` / ``c_grp`` 0 or ``M``: one group,
+    so ``a_gstride`` / ``c_gstride`` have nothing to act on); :func:`_check_glu` holds every
+    refusal."""
     import torch
 
+    if glu:
+        return _gemm_glu(a, w, out, out_scale, out_quant=out_quant, out_dtype=out_dtype,
+                         tile=tile, mode=mode, M=M, a_grp=a_grp, c_grp=c_grp, stream=stream,
+                         act=act, ksplit=ksplit, a_scale=a_scale, w_scale=w_scale)
     if out_quant is None and out_scale is not None:
         raise ValueError("out_scale goes with out_quant")
     if out_quant is not None:

@@ -10,6 +10,13 @@ the minimum and the round-to-round spread (max - min over the rounds, as a share
 ``not slower`` means: the fused median is at most the pair's plus the larger of the two spreads.
 
     python scripts/bench_qout.py --json out/qout.json
+
+``--gated`` times the gated fc1 instead (``act = silu``, ``W = pack_glu(Wg, Wu)`` of ``2 N`` rows
+for a shape's ``N``): ``fused`` is ``gemm(..., glu=True, out_quant=)``, one launch; ``chain`` is
+what it replaces, the ungated GEMM to a bf16 ``[M, 2N]`` intermediate, torch's ``silu(g) * u`` on
+its halves, then the streaming quantiser.
+
+    python scripts/bench_qout.py --gated --json out/qout_gated.json
 """
 
 from __future__ import annotations
@@ -62,6 +69,68 @@ def run_rounds(variants, rounds, iters):
     return times
 
 
+def run_gated(a, shapes, g):
+    """The fused gated fc1 against the unfused chain, per shape, input and output form."""
+    import torch
+
+    from ddlb_amd.ops.gemm import gemm, pack_glu
+    from ddlb_amd.ops.mx import quantize_mx, quantize_mxfp4
+
+    quant = {"mx": quantize_mx, "mxfp4": quantize_mxfp4}
+    results = []
+    for (M, F, K) in shapes:
+        X = (torch.rand((M, K), generator=g, device="cuda") * 2 - 1).to(torch.bfloat16)
+        Wg, Wu = ((torch.rand((F, K), generator=g, device="cuda") * 2 - 1).to(torch.bfloat16)
+                  * K ** -0.5 for _ in range(2))
+        Wt = pack_glu(Wg, Wu)
+        a8, sa8 = quantize_mx(X)
+        w8, sw8 = quantize_mx(Wt)
+        inputs = {"bf16": (X, Wt, {}), "mxfp8": (a8, w8, dict(a_scale=sa8, w_scale=sw8))}
+        bf = torch.empty((M, 2 * F), dtype=torch.bfloat16, device="cuda")
+        halves = bf.view(M, F // 32, 2, 32)
+        variants = {}
+        for form, (xa, xw, kw) in inputs.items():
+            for fmt in FMTS:
+                ncol = F if fmt == "mx" else F // 2
+                q = torch.empty((M, ncol), dtype=torch.uint8, device="cuda").view(
+                    torch.float8_e4m3fn if fmt == "mx" else torch.float4_e2m1fn_x2)
+                s = torch.empty((M, F // 32), dtype=torch.uint8, device="cuda")
+
+                def fused(xa=xa, xw=xw, kw=kw, fmt=fmt, q=q, s=s):
+                    gemm(xa, xw, q, tile=a.tile, act="silu", glu=True, out_quant=fmt,
+                         out_scale=s, **kw)
+
+                def chain(xa=xa, xw=xw, kw=kw, fmt=fmt):
+                    gemm(xa, xw, bf, tile=a.tile, **kw)
+                    h = torch.nn.functional.silu(halves[:, :, 0]) * halves[:, :, 1]
+                    quant[fmt](h.reshape(M, F))
+
+                variants[f"{form}->{fmt} fused"] = fused
+                variants[f"{form}->{fmt} pair"] = chain
+        times = run_rounds(variants, a.rounds, a.iters)
+        print(f"\ngated fc1 {M}x{2 * F}x{K} -> [{M}, {F}]  silu  tile={a.tile}")
+        for form in inputs:
+            for fmt in FMTS:
+                c = compare(times, f"{form}->{fmt} fused", f"{form}->{fmt} pair")
+                c.update(M=M, N=2 * F, K=K, input=form, out=fmt, tile=a.tile, act="silu")
+                results.append(c)
+                print(f"  {form:6s}-> {fmt:6s} fused {c['fused']['ms_median']:8.4f} ms "
+                      f"(spread {100 * c['fused']['spread']:4.1f} %)   chain "
+                      f"{c['pair']['ms_median']:8.4f} ms "
+                      f"(spread {100 * c['pair']['spread']:4.1f} %)"
+                      f"   x{c['speedup']:.3f}  {'ok' if c['not_slower'] else 'SLOWER'}")
+        del X, Wg, Wu, Wt, a8, w8, bf, halves, variants, inputs
+        torch.cuda.empty_cache()
+    return results
+
+
+def dump(path, results):
+    if path:
+        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+        with open(path, "w") as f:
+            json.dump(results, f, indent=1)
+
+
 def main():
     import torch
 
@@ -75,6 +144,8 @@ def main():
     p.add_argument("--shapes", default="all", help="all, or indices into SHAPES")
     p.add_argument("--tile", default="auto")
     p.add_argument("--no-mlp", action="store_true")
+    p.add_argument("--gated", action="store_true",
+                   help="the gated (GLU) fc1, fused against GEMM + torch silu(g) * u + quantiser")
     p.add_argument("--json", default=None)
     a = p.parse_args()
     if not torch.cuda.is_available():
@@ -84,6 +155,9 @@ def main():
     shapes = SHAPES if a.shapes == "all" else [SHAPES[int(i)] for i in a.shapes.split(",")]
     quant = {"mx": quantize_mx, "mxfp4": quantize_mxfp4}
     results = {"gemm": [], "mlp": []}
+    if a.gated:  # (no MLP part: --no-mlp changes nothing here)
+        dump(a.json, {"gated": run_gated(a, shapes, g)})
+        return
     for (M, N, K) in shapes:
         X = (torch.rand((M, K), generator=g, device="cuda") * 2 - 1).to(torch.bfloat16)
         Wt = (torch.rand((N, K), generator=g, device="cuda") * 2 - 1).to(torch.bfloat16)
@@ -141,10 +215,7 @@ def main():
                   f"{'ok' if c['not_slower'] else 'SLOWER'}")
         del mlps
         torch.cuda.empty_cache()
-    if a.json:
-        os.makedirs(os.path.dirname(a.json) or ".", exist_ok=True)
-        with open(a.json, "w") as f:
-            json.dump(results, f, indent=1)
+    dump(a.json, results)
 
 
 if __name__ == "__main__":
