@@ -182,6 +182,39 @@ PYBIND11_MODULE(_C, m) {
         py::arg("act") = 0, py::arg("ksplit") = 1, py::arg("a_scale") = 0,
         py::arg("b_scale") = 0, py::arg("a_scale_ld") = 0, py::arg("b_scale_ld") = 0,
         py::arg("c_scale") = 0, py::arg("c_scale_ld") = 0, py::arg("glu") = 0);
+  // Grouped GEMM (GemmArgs::grp_offs): group g = rows [offs[g], offs[g + 1]) of a / c (M rows in
+  // all) times the weight at b + g * b_gstride elements; offs is device memory, never read here.
+  m.def("gemm_grouped",
+        [](uintptr_t a, uintptr_t b, uintptr_t c, uintptr_t offs, int ngroups, int64_t lda,
+           int64_t ldb, int64_t ldc, int64_t b_gstride, int M, int N, int K, int din, int dout,
+           int tile, uintptr_t stream, int act, uintptr_t a_scale, uintptr_t b_scale,
+           int64_t a_scale_ld, int64_t b_scale_ld, int64_t b_scale_gstride, uintptr_t c_scale,
+           int64_t c_scale_ld, int glu) {
+          GemmArgs g = make_args(a, b, c, lda, ldb, ldc, M, N, K, 0, 0, 0, 0);
+          g.grp_offs = (const int*)offs;
+          g.ngroups = ngroups;
+          g.b_gstride = b_gstride;
+          g.act = act;
+          g.a_scale = (const uint8_t*)a_scale;
+          g.b_scale = (const uint8_t*)b_scale;
+          g.a_scale_ld = a_scale_ld;
+          g.b_scale_ld = b_scale_ld;
+          g.b_scale_gstride = b_scale_gstride;
+          g.c_scale = (uint8_t*)c_scale;
+          g.c_scale_ld = c_scale_ld;
+          g.glu = glu != 0;
+          // a null offsets pointer or ngroups = 0 must be refused, not run ungrouped
+          if (offs == 0 || ngroups <= 0) check(hipErrorInvalidValue, "gemm_grouped");
+          check(gemm_launch(g, din, dout, tile, GEMM_MODE_AUTO, (hipStream_t)stream),
+                "gemm_grouped");
+        },
+        py::arg("a"), py::arg("b"), py::arg("c"), py::arg("offs"), py::arg("ngroups"),
+        py::arg("lda"), py::arg("ldb"), py::arg("ldc"), py::arg("b_gstride"), py::arg("M"),
+        py::arg("N"), py::arg("K"), py::arg("din"), py::arg("dout"), py::arg("tile") = 0,
+        py::arg("stream") = 0, py::arg("act") = 0, py::arg("a_scale") = 0,
+        py::arg("b_scale") = 0, py::arg("a_scale_ld") = 0, py::arg("b_scale_ld") = 0,
+        py::arg("b_scale_gstride") = 0, py::arg("c_scale") = 0, py::arg("c_scale_ld") = 0,
+        py::arg("glu") = 0);
   // x[R, K] f32 / f16 / bf16 -> q[R, K] e4m3 + s[R, K / 32] E8M0 bytes; mxfp4_quantize: the same
   // -> q[R, K / 2] E2M1 nibble pairs (ldq in bytes) + s
   def_row_quantizer(m, "mx_quantize", mx_quantize_launch);

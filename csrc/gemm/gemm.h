@@ -197,12 +197,26 @@ struct GemmArgs {
   // the number of b rows; N % 64 == 0 (whole blocks as the reader takes them for a quantised
   // output: N % 256, fp4 N % 512); ldc >= N / 2. Plain rows only.
   int glu = 0;
+  // Grouped form (optional; the tiled kernel, codes of mxs_offers()): grp_offs is a DEVICE array of
+  // ngroups + 1 int32 row offsets, read by the kernel only (no host sync). Group g is rows
+  // [o'[g], o'[g + 1]) of a, a_scale, c and c_scale and multiplies by the weight at
+  // b + g * b_gstride ELEMENTS with the scales at b_scale + g * b_scale_gstride BYTES; every
+  // flavour the tiled kernel has (dense, block-scaled, act, quantised output, glu) per group, bit
+  // for bit what the ungrouped launch writes for those rows. M is the number of rows of a the
+  // launch may touch (T). The offsets are clamped as they are read, o'[0] = clamp(o[0], 0, T),
+  // o'[g + 1] = clamp(o[g + 1], o'[g], T): no content of the array addresses a row >= T, rows
+  // outside [o'[0], o'[ngroups]) are not written, empty groups are legal anywhere.
+  // 1 <= ngroups <= kMaxGroups. Plain rows only.
+  const int* grp_offs = nullptr;
+  int ngroups = 0;
+  int64_t b_gstride = 0, b_scale_gstride = 0;
 };
+constexpr int kMaxGroups = 1024;
 // The byte view of a launch whose operands and / or output are fp4: the kernels address bytes (two
 // E2M1 elements each), so K, lda and ldb of fp4 operands and ldc of an fp4 output are halved.
 // GemmArgs stay in ELEMENTS up to the launch entries (gemm_entry.h); the view is formed inside.
 constexpr GemmArgs fp4_byte_view(GemmArgs p, bool fp4_in, bool fp4_out) {
-  if (fp4_in) { p.K /= 2; p.lda /= 2; p.ldb /= 2; }
+  if (fp4_in) { p.K /= 2; p.lda /= 2; p.ldb /= 2; p.b_gstride /= 2; }
   if (fp4_out) p.ldc /= 2;
   return p;
 }

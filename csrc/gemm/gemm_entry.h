@@ -22,6 +22,22 @@ hipError_t launch_fast_mx4(const GemmArgs& p, int dout, int tile, hipStream_t s)
 hipError_t launch_qout_fp8(const GemmArgs& p, int din, int tile, hipStream_t s);
 hipError_t launch_qout_fp4(const GemmArgs& p, int din, int tile, hipStream_t s);
 hipError_t launch_generic(const GemmArgs& p, int din, int dout, hipStream_t s);
+// Grouped launches (GemmArgs::grp_offs): gemm_launch calls launch_grouped (gemm_grouped.hip), which
+// picks the translation unit by operands (bf16, f16, fp8 with scales, fp4 with scales) and output
+// (dense: gemm_grouped_<in>.hip; fp8 / fp4 with c_scale: gemm_grouped_<in>_q.hip).
+// launch_grouped is declared weak so that a host program which links gemm_mfma.hip against its own
+// set of entries without this one still links; gemm_launch answers hipErrorNotSupported for a
+// grouped launch where it is absent, and the extension always holds it.
+hipError_t launch_grouped(const GemmArgs& p, int din, int dout, int tile, hipStream_t s)
+    __attribute__((weak));
+hipError_t launch_grouped_bf16(const GemmArgs& p, int dout, int tile, hipStream_t s);
+hipError_t launch_grouped_f16(const GemmArgs& p, int dout, int tile, hipStream_t s);
+hipError_t launch_grouped_mxs(const GemmArgs& p, int dout, int tile, hipStream_t s);
+hipError_t launch_grouped_mx4(const GemmArgs& p, int dout, int tile, hipStream_t s);
+hipError_t launch_grouped_bf16_q(const GemmArgs& p, int dout, int tile, hipStream_t s);
+hipError_t launch_grouped_f16_q(const GemmArgs& p, int dout, int tile, hipStream_t s);
+hipError_t launch_grouped_mxs_q(const GemmArgs& p, int dout, int tile, hipStream_t s);
+hipError_t launch_grouped_mx4_q(const GemmArgs& p, int dout, int tile, hipStream_t s);
 
 // Dispatch of the fast (MFMA) family by dtype pair; hipErrorInvalidValue if not provided.
 inline hipError_t launch_fast(const GemmArgs& p, int din, int dout, int tile, hipStream_t s) {

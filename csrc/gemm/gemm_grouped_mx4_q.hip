@@ -1,0 +1,11 @@
+// gemm_grouped_mx4_q: the grouped form of the tiled kernel (GemmArgs::grp_offs;
+// gemm_tn_grouped_kernel, gemm_grouped_kernels.h), ungated and gated, the four codes of
+// mxs_offers(): block-scaled fp4 operands, MX-fp8 / MXFP4 out.
+#include "gemm_grouped_kernels.h"
+#include "gemm_entry.h"
+
+namespace ddlb {
+hipError_t launch_grouped_mx4_q(const GemmArgs& p, int dout, int tile, hipStream_t s) {
+  return launch_grouped_t<MmaMX4S, DT_FP4, true>(p, dout, tile, s);
+}
+}  // namespace ddlb

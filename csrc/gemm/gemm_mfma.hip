@@ -40,6 +40,7 @@
 
 #include "gemm.h"
 #include "gemm_entry.h"
+#include "tile_map.h"
 
 namespace ddlb {
 
@@ -110,6 +111,44 @@ static hipError_t plain_operands_only(const GemmArgs& p, bool plain_c_rows, bool
   return hipSuccess;
 }
 
+// Grouped launches (GemmArgs::grp_offs): what a grouped launch adds to the checks of the flavour it
+// runs (the functions below, with M = T, the rows the launch may touch). The offsets are device
+// memory and are never read here. Plain rows in the launch's own order only, the tiled kernel's
+// offered codes, no generic mode; the weights of consecutive groups b_gstride elements apart
+// without overlap and as aligned as b itself, their scales b_scale_gstride bytes apart on the
+// scale words' alignment; a grid bound (tile_map.h) that is a grid.
+static bool grouped_launch(const GemmArgs& p) { return p.grp_offs != nullptr || p.ngroups != 0; }
+static hipError_t grouped_operands_ok(const GemmArgs& p, int din, int tile, int mode) {
+  if (p.grp_offs == nullptr || p.ngroups <= 0 || p.ngroups > kMaxGroups)
+    return hipErrorInvalidValue;
+  if (din != DT_BF16 && din != DT_F16 && din != DT_FP8 && din != DT_FP4)
+    return hipErrorInvalidValue;
+  if (mode == GEMM_MODE_GENERIC || (tile != TILE_AUTO && !mxs_offers(tile)))
+    return hipErrorInvalidValue;
+  if (p.M < 0 || p.N < 0) return hipErrorInvalidValue;
+  const hipError_t e = plain_operands_only(p, true, true, hipErrorInvalidValue);
+  if (e != hipSuccess) return e;
+  const int64_t esz2 = din == DT_FP4 ? 1 : 2 * dtype_size(din);  // twice the element size
+  if (p.b_gstride < 0 || p.b_gstride * esz2 % 32 ||
+      (p.ngroups > 1 && p.b_gstride < (int64_t)p.N * p.ldb))
+    return hipErrorInvalidValue;
+  if (p.b_scale != nullptr) {
+    const int align = din == DT_FP4 ? 8 : 4;
+    if (p.b_scale_gstride < 0 || p.b_scale_gstride % align ||
+        (p.ngroups > 1 && p.b_scale_gstride < (int64_t)p.N * p.b_scale_ld))
+      return hipErrorInvalidValue;
+  }
+  if (grouped_grid_bound(p.M, p.ngroups, 128, (p.N + 127) / 128) > 0x7FFFFFFFLL)
+    return hipErrorInvalidValue;
+  return hipSuccess;
+}
+// The entry of a checked grouped launch (weak: gemm_entry.h).
+static hipError_t launch_grouped_checked(const GemmArgs& p, int din, int dout, int tile,
+                                         hipStream_t s) {
+  if (launch_grouped == nullptr) return hipErrorNotSupported;
+  return launch_grouped(p, din, dout, tile, s);
+}
+
 // DT_FP4 operands: the block-scaled MXFP4 flavour of the tiled kernel or hipErrorInvalidValue,
 // never a launch with something substituted.
 static hipError_t gemm_launch_fp4(const GemmArgs& p, int dout, int tile, int mode, hipStream_t s) {
@@ -130,6 +169,7 @@ static hipError_t gemm_launch_fp4(const GemmArgs& p, int dout, int tile, int mod
   if (!scale_operands_ok(p, 8)) return hipErrorInvalidValue;
   if (tile == TILE_AUTO) tile = mxs_tile_for(choose_tile(p.M, p.N, p.K, DT_FP4));
   if (tile < 0) return hipErrorInvalidValue;
+  if (grouped_launch(p)) return launch_grouped_checked(p, DT_FP4, dout, tile, s);
   return launch_fast_mx4(p, dout, tile, s);
 }
 
@@ -171,6 +211,7 @@ static hipError_t gemm_launch_qout(const GemmArgs& p, int din, int dout, int til
     return hipErrorInvalidValue;
   if (tile == TILE_AUTO) tile = mxs_tile_for(choose_tile(p.M, p.N, p.K, din));
   if (tile < 0) return hipErrorInvalidValue;
+  if (grouped_launch(p)) return launch_grouped_checked(p, din, dout, tile, s);
   return q4 ? launch_qout_fp4(p, din, tile, s) : launch_qout_fp8(p, din, tile, s);
 }
 
@@ -218,10 +259,36 @@ static hipError_t gemm_launch_glu(const GemmArgs& p, int din, int dout, int tile
   if (tile < 0) return hipErrorInvalidValue;
   GemmArgs g = p;
   g.glu = 1;
+  if (grouped_launch(p)) return launch_grouped_checked(g, din, dout, tile, s);
   if (qout) return q4 ? launch_qout_fp4(g, din, tile, s) : launch_qout_fp8(g, din, tile, s);
   if (in4) return launch_fast_mx4(g, dout, tile, s);
   if (scaled) return launch_fast_mxs(g, dout, tile, s);
   return launch_fast(g, din, dout, tile, s);
+}
+
+// A grouped launch with bf16 / f16 operands or block-scaled fp8 ones and a dense output (the gated,
+// quantising and fp4 forms go through the functions above): the grouped tiled kernel or
+// hipErrorInvalidValue. Unit-scale fp8 has no grouped form.
+static hipError_t gemm_launch_grouped_dense(const GemmArgs& p, int din, int dout, int tile,
+                                            int mode, hipStream_t s) {
+  const bool scaled = din == DT_FP8;
+  if (din != DT_BF16 && din != DT_F16 && !scaled) return hipErrorInvalidValue;
+  if (scaled ? (p.a_scale == nullptr || p.b_scale == nullptr)
+             : (p.a_scale != nullptr || p.b_scale != nullptr))
+    return hipErrorInvalidValue;
+  if (dout != DT_F32 && !(scaled ? dout == DT_BF16 || dout == DT_F16 : dout == din))
+    return hipErrorInvalidValue;
+  if (mode < GEMM_MODE_AUTO || mode > GEMM_MODE_MX || (!scaled && mode == GEMM_MODE_MX))
+    return hipErrorInvalidValue;
+  if (p.K <= 0) return hipErrorInvalidValue;
+  if (p.M == 0 || p.N == 0) return hipSuccess;
+  if (p.a == nullptr || p.b == nullptr || p.c == nullptr || p.lda < p.K || p.ldb < p.K ||
+      p.ldc < p.N || !gemm_fast_path_ok(p, din, dout))
+    return hipErrorInvalidValue;
+  if (scaled && !scale_operands_ok(p, 4)) return hipErrorInvalidValue;
+  if (tile == TILE_AUTO) tile = mxs_tile_for(choose_tile(p.M, p.N, p.K, din));
+  if (tile < 0) return hipErrorInvalidValue;
+  return launch_grouped_checked(p, din, dout, tile, s);
 }
 
 hipError_t gemm_launch(const GemmArgs& p_in, int din, int dout, int tile, int mode,
@@ -231,11 +298,17 @@ hipError_t gemm_launch(const GemmArgs& p_in, int din, int dout, int tile, int mo
   if (p.c_grp <= 0) { p.c_grp = p.M > 0 ? p.M : 1; p.c_gstride = p.c_grp; }
   // known codes only (the retired families' codes are refused, not rerouted)
   if (tile != TILE_AUTO && tile_slot(tile) < 0) return hipErrorInvalidValue;
+  const bool grouped = grouped_launch(p);
+  if (grouped) {
+    const hipError_t e = grouped_operands_ok(p, din, tile, mode);
+    if (e != hipSuccess) return e;
+  }
   if (p.glu) return gemm_launch_glu(p, din, dout, tile, mode, s);
   // quantised output: dout fp8 / fp4 and output scales go together
   if (dout == DT_FP8 || dout == DT_FP4) return gemm_launch_qout(p, din, dout, tile, mode, s);
   if (p.c_scale != nullptr) return hipErrorInvalidValue;
   if (din == DT_FP4) return gemm_launch_fp4(p, dout, tile, mode, s);
+  if (grouped) return gemm_launch_grouped_dense(p, din, dout, tile, mode, s);
   // MX block scales: both or neither; with them the tiled kernel's scaled flavour or a refusal,
   // never unit scales in their place
   if ((p.a_scale != nullptr) != (p.b_scale != nullptr)) return hipErrorInvalidValue;

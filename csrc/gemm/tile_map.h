@@ -79,6 +79,63 @@ __host__ __device__ inline void tile_mn(const GemmArgs& p, int wg, int tiles_m, 
   tn = in / gs;
 }
 
+// ---------------------------------------------------------------- grouped GEMM (grp_offs)
+// Group g owns rows [o'[g], o'[g + 1]) of A and C, with the offsets clamped as they are read:
+// o'[0] = clamp(o[0], 0, T), o'[g + 1] = clamp(o[g + 1], o'[g], T). Whatever the array holds, the
+// clamped offsets are monotone and inside [0, T], so no group addresses a row >= T.
+__host__ __device__ inline int grouped_clamp(int v, int lo, int hi) {
+  return v < lo ? lo : (v > hi ? hi : v);
+}
+
+// Workgroups of a grouped launch: tiles_n times an upper bound of the number of m-tiles, which the
+// host cannot know (the offsets are read on the device only). With n_g rows in group g,
+//   sum_g ceil(n_g / BM) <= sum_g (floor(n_g / BM) + 1) <= floor(sum_g n_g / BM) + E <= T / BM + E
+// (a sum of floors is at most the floor of the sum, and sum_g n_g <= T), and every term is at
+// most ceil(T / BM), so the sum is at most ceil(T / BM) * E as well. 64-bit: the caller refuses
+// what does not fit a grid.
+__host__ __device__ inline int64_t grouped_grid_bound(int T, int E, int BM, int tiles_n) {
+  const int64_t a = (int64_t)(T / BM) + E, b = ((int64_t)T + BM - 1) / BM * E;
+  return (int64_t)tiles_n * (a < b ? a : b);
+}
+
+// Workgroup index -> tile of a grouped launch, or "no tile" (false) for the surplus of the grid
+// bound. M-tiles are numbered group after group (an empty group has none), n-tiles fastest, so
+// wg / tiles_n is an m-tile of the whole launch and the scan below finds its group. The scan reads
+// the offsets eight at a time (the loads of a chunk are independent and issued together; an index
+// past E re-reads o[E], which clamps to an empty group) and stops after the chunk that holds the
+// tile. Every quantity is uniform over the workgroup: scalar loads and scalar arithmetic.
+struct GroupTile {
+  int g, tm, tn;   // group, m-tile within the group, n-tile
+  int row0, rows;  // the group's first row (of T) and its number of rows (> 0)
+};
+__host__ __device__ inline bool grouped_tile(const int* offs, int T, int E, int BM, int tiles_n,
+                                             int wg, GroupTile& t) {
+  const int mt = wg / tiles_n;
+  int lo = grouped_clamp(offs[0], 0, T), acc = 0;
+  bool found = false;
+  for (int g0 = 0; g0 < E && !found; g0 += 8) {
+    int o[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = offs[g0 + j + 1 < E ? g0 + j + 1 : E];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int hi = grouped_clamp(o[j], lo, T);
+      const int nt = (hi - lo) / BM + ((hi - lo) % BM != 0);
+      if (!found && mt < acc + nt) {
+        found = true;
+        t.g = g0 + j;
+        t.tm = mt - acc;
+        t.tn = wg - mt * tiles_n;
+        t.row0 = lo;
+        t.rows = hi - lo;
+      }
+      acc += nt;
+      lo = hi;
+    }
+  }
+  return found;
+}
+
 // In-kernel all-gather work unit u -> (block b, producer prod, part pi): block-major; within a
 // block, consecutive units go to different producers (ring order from rank + 1), so the copy
 // workgroups in flight spread over every peer / xGMI link.

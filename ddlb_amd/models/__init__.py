@@ -5,6 +5,8 @@
 * :mod:`ddlb_amd.models.tp_mlp`  — sequence-parallel TP MLP block (AG+GEMM+act -> GEMM+RS).
 * :mod:`ddlb_amd.models.mx_mlp`  — one-GPU MLP on the block-scaled matrix pipe (MX-fp8 / MXFP4):
   fc1 writes its activation quantised from the GEMM epilogue, fc2 reads it.
+* :mod:`ddlb_amd.models.mx_moe`  — one-GPU routed (mixture-of-experts) gated FFN: tokens sorted by
+  expert on the device, one grouped GEMM launch per layer (``ops.gemm.gemm_grouped``).
 * :mod:`ddlb_amd.models.mx_linear` — a trainable one-GPU MX linear layer: forward, dgrad and
   wgrad on the block-scaled GEMMs, operands quantised along each GEMM's own contraction axis.
 """

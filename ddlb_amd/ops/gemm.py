@@ -15,6 +15,8 @@ scales with ``a_scale`` / ``w_scale``, see :mod:`ddlb_amd.ops.mx`), float4_e2m1f
 data and E8M0 scales per 32 output columns, quantised in the GEMM's epilogue.
 ``glu=True``: the same operands, ``w`` holding interleaved gate and up rows (``pack_glu``); the
 epilogue writes ``act(gate) * up``, half as many columns, dense or quantised.
+``gemm_grouped(a, w, offsets)``: per-expert weights ``w [E, N, K]`` over contiguous runs of rows
+of ``a`` given by device-side int32 offsets, one launch, every form above on the tiled kernel.
 """
 
 from __future__ import annotations
@@ -704,3 +706,230 @@ def fast_path_ok(a, w, out) -> bool:
     return bool(C.gemm_fast_path_ok(a.data_ptr(), w.data_ptr(), out.data_ptr(), a.stride(0),
                                     w.stride(0), out.stride(0), a.shape[0], w.shape[0],
                                     a.shape[1], dtype_code(a.dtype), dtype_code(out.dtype)))
+
+
+# ---------------------------------------------------------------- grouped GEMM (per-expert weights)
+MAX_GROUPS = 1024  # gemm.h kMaxGroups
+
+
+def pack_glu_grouped(gate, up):
+    """:func:`pack_glu` per expert: ``[E, F, K]`` gate and up rows -> the ``[E, 2F, K]`` weight
+    ``gemm_grouped(glu=True)`` reads. Any dtype, scales included."""
+    import torch
+
+    if gate.dim() != 3 or up.dim() != 3 or gate.shape != up.shape or gate.dtype != up.dtype:
+        raise ValueError(f"pack_glu_grouped takes two 3-D tensors of one shape and dtype, not "
+                         f"{tuple(gate.shape)} {gate.dtype} and {tuple(up.shape)} {up.dtype}")
+    E, F, K = gate.shape
+    if F % GLU_GROUP:
+        raise ValueError(f"pack_glu_grouped needs F % {GLU_GROUP} == 0 (F = {F})")
+    g, u = (_as_bytes(t).reshape(E, F // GLU_GROUP, GLU_GROUP, K) for t in (gate, up))
+    return torch.stack((g, u), dim=2).reshape(E, 2 * F, K).view(gate.dtype)
+
+
+def clamp_offsets(offsets, T: int):
+    """The offsets as the grouped kernel uses them (a Python list): ``o'[0] = clamp(o[0], 0, T)``,
+    ``o'[g + 1] = clamp(o[g + 1], o'[g], T)``. Reads the tensor on the host."""
+    o = [int(v) for v in offsets.tolist()]
+    out = [min(max(o[0], 0), T)]
+    for v in o[1:]:
+        out.append(min(max(v, out[-1]), T))
+    return out
+
+
+def grouped_reference(a, w, offsets):
+    """The specification of :func:`gemm_grouped` on dense operands, as an f32 torch loop on any
+    device: rows ``[o'[g], o'[g + 1])`` of the ``[T, N]`` result are ``a[rows] @ w[g].T`` with the
+    offsets clamped by :func:`clamp_offsets`; every other row is zero."""
+    import torch
+
+    if a.dim() != 2 or w.dim() != 3 or a.shape[1] != w.shape[2]:
+        raise ValueError(f"grouped_reference takes a [T, K] and w [E, N, K], not "
+                         f"{tuple(a.shape)} and {tuple(w.shape)}")
+    if offsets.dim() != 1 or offsets.shape[0] != w.shape[0] + 1:
+        raise ValueError(f"offsets must have shape ({w.shape[0] + 1},), not {tuple(offsets.shape)}")
+    T = a.shape[0]
+    o = clamp_offsets(offsets, T)
+    out = torch.zeros((T, w.shape[1]), dtype=torch.float32, device=a.device)
+    for g in range(w.shape[0]):
+        if o[g + 1] > o[g]:
+            out[o[g]:o[g + 1]] = a[o[g]:o[g + 1]].float() @ w[g].float().t()
+    return out
+
+
+def _check_grouped(a, w, offsets, out=None, out_scale=None, *, out_dtype=None,
+                   tile: str = "auto", act: str = "none", a_scale=None, w_scale=None,
+                   out_quant: Optional[str] = None, glu: bool = False):
+    """Every refusal of the grouped GEMM, on the host and before anything is loaded or launched
+    (CPU tensors pass through it; the offsets' content is never read). What the ungrouped forms
+    already refuse is refused by their own checks (:func:`_check_block_scaled`,
+    :func:`_check_out_quant`, :func:`_check_glu`), applied to ``a`` and an expert's slice of ``w``
+    and ``w_scale``. Returns ``(T, N, K, E, output dtype)``: ``N`` the rows of an expert's weight."""
+    import torch
+
+    if act not in ACTS:
+        raise ValueError(f"unknown activation {act!r}")
+    if not isinstance(w, torch.Tensor) or w.dim() != 3:
+        raise ValueError(f"a grouped GEMM takes w as [E, N, K] (3-D), not "
+                         f"{tuple(getattr(w, 'shape', ()))}")
+    if a.dim() != 2:
+        raise ValueError(f"a grouped GEMM takes a as [T, K] (2-D), not {tuple(a.shape)}")
+    E, N = w.shape[0], w.shape[1]
+    T = a.shape[0]
+    if E < 1:
+        raise ValueError("a grouped GEMM needs at least one group")
+    if E > MAX_GROUPS:
+        raise ValueError(f"a grouped GEMM takes at most {MAX_GROUPS} groups, not {E}")
+    if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int32:
+        raise TypeError(f"offsets must be an int32 tensor, not "
+                        f"{getattr(offsets, 'dtype', type(offsets))}")
+    if offsets.dim() != 1 or offsets.shape[0] != E + 1 or not offsets.is_contiguous():
+        raise ValueError(f"offsets must be contiguous with shape ({E + 1},) for {E} groups, not "
+                         f"{tuple(offsets.shape)}")
+    if offsets.device != a.device:
+        raise ValueError(f"offsets is on {offsets.device}, the operands on {a.device}")
+    if w.device != a.device:
+        raise ValueError("operands on different devices")
+    if tile != "auto" and tile not in SCALED_TILES:
+        raise ValueError(f"a grouped GEMM is offered for tile auto / {SCALED_TILES}, not {tile!r} "
+                         "(the ping-pong, interleaved and 256x256 kernels have no grouped form)")
+    fp4 = _is_fp4(a) or _is_fp4(w)
+    fp8 = a.dtype == torch.float8_e4m3fn or w.dtype == torch.float8_e4m3fn
+    if not fp4 and not fp8 and a.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"a grouped GEMM takes bf16, f16, scaled fp8 or scaled fp4 operands, not "
+                        f"{a.dtype}")
+    if a.dtype != w.dtype:
+        raise TypeError(f"A dtype {a.dtype} != W dtype {w.dtype}")
+    if (fp8 or fp4) and (a_scale is None or w_scale is None):
+        raise ValueError("a grouped GEMM on fp8 / fp4 operands needs a_scale and w_scale (the "
+                         "unit-scale kernels have no grouped form)")
+    if w.stride(2) != 1 or w.stride(1) < w.shape[2] or (E > 1 and w.stride(0) < N * w.stride(1)):
+        raise ValueError(f"w needs unit inner stride, rows of at least K and experts at least "
+                         f"N rows apart (strides {tuple(w.stride())})")
+    if w.stride(0) * w.element_size() % 16:
+        raise ValueError("the experts' weights must be a multiple of 16 bytes apart")
+    K = (2 if fp4 else 1) * a.shape[1]
+    scaled = fp4 or fp8
+    if scaled and w_scale is not None:
+        align = 8 if fp4 else 4
+        if not isinstance(w_scale, torch.Tensor) or w_scale.dim() != 3 or \
+                tuple(w_scale.shape) != (E, N, K // 32):
+            raise ValueError(f"w_scale must have shape {(E, N, K // 32)}, not "
+                             f"{tuple(getattr(w_scale, 'shape', ()))}")
+        if w_scale.stride(0) % align or (E > 1 and w_scale.stride(0) < N * w_scale.stride(1)):
+            raise ValueError(f"w_scale needs experts a multiple of {align} bytes and at least N "
+                             f"rows apart (strides {tuple(w_scale.stride())})")
+    elif w_scale is not None and (not isinstance(w_scale, torch.Tensor) or w_scale.dim() != 3):
+        raise TypeError(f"block scales need fp8 / fp4 operands, not {a.dtype}")
+    if out_quant is None and out_scale is not None:
+        raise ValueError("out_scale goes with out_quant")
+    if T >= 2 ** 31 or N >= 2 ** 31 or K >= 2 ** 31:
+        raise ValueError("dimensions must fit in 32 bits")
+    # what the ungrouped forms refuse, per expert slice (all slices share shape and strides; the
+    # first and the last differ in their addresses)
+    odt = None
+    for g in sorted({0, E - 1}):
+        wg, wsg = w[g], (w_scale[g] if w_scale is not None else None)
+        if glu:
+            odt = _check_glu(a, wg, out, out_scale, out_quant=out_quant, out_dtype=out_dtype,
+                             a_scale=a_scale, w_scale=wsg, tile=tile, act=act)[3]
+        elif out_quant is not None:
+            _check_out_quant(a, wg, out_quant, out, out_scale, a_scale=a_scale, w_scale=wsg,
+                             tile=tile, out_dtype=out_dtype)
+            odt = out_quant_dtype(out_quant)
+        else:
+            if a.shape[1] != wg.shape[1]:
+                raise ValueError(f"K mismatch: A {tuple(a.shape)} vs W {tuple(w.shape)}")
+            if scaled:
+                dense = (torch.bfloat16, torch.float16, torch.float32)
+                _check_block_scaled(_MX_FP4 if fp4 else _MX_FP8, a, wg, a_scale, wsg, T, tile,
+                                    "auto", 0, 0)
+            else:
+                if a_scale is not None or w_scale is not None:
+                    raise TypeError(f"block scales need fp8 / fp4 operands, not {a.dtype}")
+                dense = (a.dtype, torch.float32)
+            odt = out.dtype if out is not None else (out_dtype or dense[0])
+            if out is not None and out_dtype is not None and out_dtype != out.dtype:
+                raise TypeError(f"out is {out.dtype}, out_dtype={out_dtype}")
+            if odt not in dense:
+                raise TypeError(f"a grouped GEMM on {a.dtype} operands writes one of {dense}, "
+                                f"not {odt}")
+            if out is not None:
+                if out.device != a.device:
+                    raise ValueError(f"out is on {out.device}, the operands on {a.device}")
+                if out.dim() != 2 or out.shape[0] < T or out.shape[1] != N:
+                    raise ValueError(f"out must have shape (>= {T}, {N}), not {tuple(out.shape)}")
+                if out.stride(1) != 1 or out.stride(0) < N:
+                    raise ValueError(f"out needs unit inner stride and a row stride of at least "
+                                     f"{N} (strides {tuple(out.stride())})")
+    return T, N, K, E, odt
+
+
+def gemm_grouped(a, w, offsets, out=None, *, out_dtype=None, tile: str = "auto",
+                 act: str = "none", a_scale=None, w_scale=None, out_quant: Optional[str] = None,
+                 out_scale=None, glu: bool = False, stream=None):
+    """Grouped GEMM over per-expert weights in ONE launch: rows ``[o[g], o[g + 1])`` of ``a``
+    ``[T, K]`` are multiplied by ``w[g]`` of ``w`` ``[E, N, K]`` (unit inner stride, any
+    ``w.stride(0) >= N * w.stride(1)``; fp4: ``K / 2`` bytes per row). ``offsets`` is an int32
+    ``[E + 1]`` tensor on ``a``'s device that only the kernel reads: no host sync, so the call can
+    be captured in a graph. The kernel clamps the offsets as it reads them
+    (:func:`clamp_offsets`): nothing in the array can make it touch a row ``>= T``, and empty
+    groups are legal anywhere.
+
+    Operands and epilogues are those of ``gemm(..., glu=..., out_quant=...)`` on the tiled kernel
+    (tiles :data:`SCALED_TILES`): bf16 -> bf16 | f32, f16 -> f16 | f32, block-scaled fp8 / fp4
+    (``a_scale [T, K / 32]``, ``w_scale [E, N, K / 32]``) -> bf16 | f16 | f32, each dense, with
+    ``act``, with ``glu`` (:func:`pack_glu_grouped`), with ``out_quant`` or with both; every
+    group's rows are bit for bit what ``gemm(a[rows], w[g], tile=...)`` writes. Returns what
+    ``gemm`` returns: ``[T, N]``, ``[T, N / 2]`` with ``glu``, or ``(q, s)`` with ``out_quant``.
+
+    Rows outside ``[o'[0], o'[E])`` are not written: they are unspecified in an ``out`` (and
+    ``out_scale``) allocated here, which is never zero-filled, and untouched in one passed in.
+    :func:`_check_grouped` holds every refusal."""
+    import torch
+
+    T, N, K, E, odt = _check_grouped(a, w, offsets, out, out_scale, out_dtype=out_dtype,
+                                     tile=tile, act=act, a_scale=a_scale, w_scale=w_scale,
+                                     out_quant=out_quant, glu=glu)
+    C = load()
+    _check_placement(a)
+    if w.device.type != "cuda":
+        raise ValueError("native GEMM operands must be ROCm device tensors")
+    fp4, q4 = _is_fp4(a), out_quant == "mxfp4"
+    cols = N // 2 if glu else N
+    if out is None and out_quant is not None:
+        out = torch.empty((T, cols // 2 if q4 else cols), dtype=torch.uint8,
+                          device=a.device).view(odt)
+    elif out is None:
+        out = torch.empty((T, cols), dtype=odt, device=a.device)
+    if out_quant is not None and out_scale is None:
+        out_scale = torch.empty((T, cols // 32), dtype=torch.uint8, device=a.device)
+    _check_placement(out)
+    kb = K // 2 if fp4 else K  # the operands as the byte / element matrices the kernel reads
+    if T and N and not C.gemm_fast_path_ok(a.data_ptr(), w.data_ptr(), out.data_ptr(),
+                                           a.stride(0), w.stride(1), out.stride(0), T, N, kb,
+                                           DT_U8 if fp4 else dtype_code(a.dtype),
+                                           DT_U8 if out_quant else dtype_code(odt)):
+        raise ValueError("a grouped GEMM needs the MFMA fast path: 16-byte-aligned operand rows, "
+                         "8-byte-aligned output rows and K a whole number of 128-byte K-tiles")
+    s = stream if stream is not None else torch.cuda.current_stream(a.device).cuda_stream
+    am, cm = (2 if fp4 else 1), (2 if _is_fp4(out) else 1)
+    scaled = a_scale is not None
+    C.gemm_grouped(
+        a=a.data_ptr(), b=w.data_ptr(), c=out.data_ptr(), offs=offsets.data_ptr(), ngroups=E,
+        lda=am * a.stride(0), ldb=am * w.stride(1), ldc=cm * out.stride(0),
+        b_gstride=am * w.stride(0), M=T, N=N, K=K,
+        din=DT_FP4 if fp4 else dtype_code(a.dtype),
+        dout=DT_FP4 if cm == 2 else dtype_code(out.dtype), tile=TILES[tile], stream=s,
+        act=ACTS[act], a_scale=a_scale.data_ptr() if scaled else 0,
+        b_scale=w_scale.data_ptr() if scaled else 0,
+        a_scale_ld=a_scale.stride(0) if scaled else 0,
+        b_scale_ld=w_scale.stride(1) if scaled else 0,
+        b_scale_gstride=w_scale.stride(0) if scaled else 0,
+        c_scale=out_scale.data_ptr() if out_scale is not None else 0,
+        c_scale_ld=out_scale.stride(0) if out_scale is not None else 0, glu=1 if glu else 0)
+    if stream is not None:  # the outputs stay allocated until that stream reaches them
+        out.record_stream(torch.cuda.ExternalStream(s))
+        if out_scale is not None:
+            out_scale.record_stream(torch.cuda.ExternalStream(s))
+    return out if out_quant is None else (out[:T], out_scale[:T])
