@@ -215,6 +215,52 @@ PYBIND11_MODULE(_C, m) {
         py::arg("b_scale") = 0, py::arg("a_scale_ld") = 0, py::arg("b_scale_ld") = 0,
         py::arg("b_scale_gstride") = 0, py::arg("c_scale") = 0, py::arg("c_scale_ld") = 0,
         py::arg("glu") = 0);
+  // K-grouped GEMM (GemmArgs::kgrouped): c[g] = a[:, cols g] b[:, cols g]^T under the scales of
+  // the same columns, the groups' column ranges derived from offs (clamped to rows) on the device;
+  // K is the operands' column extent, c_gstride the elements between the groups' outputs.
+  m.def("gemm_kgrouped",
+        [](uintptr_t a, uintptr_t b, uintptr_t c, uintptr_t offs, int ngroups, int rows,
+           int64_t lda, int64_t ldb, int64_t ldc, int64_t c_gstride, int M, int N, int K, int din,
+           int dout, int tile, uintptr_t stream, uintptr_t a_scale, uintptr_t b_scale,
+           int64_t a_scale_ld, int64_t b_scale_ld) {
+          GemmArgs g = make_args(a, b, c, lda, ldb, ldc, M, N, K, 0, 0, 0, 0);
+          g.grp_offs = (const int*)offs;
+          g.ngroups = ngroups;
+          g.kgrouped = 1;
+          g.kgrp_rows = rows;
+          g.c_kgstride = c_gstride;
+          g.a_scale = (const uint8_t*)a_scale;
+          g.b_scale = (const uint8_t*)b_scale;
+          g.a_scale_ld = a_scale_ld;
+          g.b_scale_ld = b_scale_ld;
+          check(gemm_launch(g, din, dout, tile, GEMM_MODE_AUTO, (hipStream_t)stream),
+                "gemm_kgrouped");
+        },
+        py::arg("a"), py::arg("b"), py::arg("c"), py::arg("offs"), py::arg("ngroups"),
+        py::arg("rows"), py::arg("lda"), py::arg("ldb"), py::arg("ldc"), py::arg("c_gstride"),
+        py::arg("M"), py::arg("N"), py::arg("K"), py::arg("din"), py::arg("dout"),
+        py::arg("tile") = 0, py::arg("stream") = 0, py::arg("a_scale") = 0,
+        py::arg("b_scale") = 0, py::arg("a_scale_ld") = 0, py::arg("b_scale_ld") = 0);
+  m.def("mx_quantize_t_grouped",  // x[T, C], rows grouped by offs -> qt / st in the padded K
+        // layout of gemm_kgrouped, or (stacked_rows > 0) one [C, R] slab per group
+        [](uintptr_t x, uintptr_t qt, uintptr_t st, uintptr_t offs, int ngroups, int64_t ldx,
+           int64_t ldqt, int64_t ldst, int T, int C, int din, bool fp4, int stacked_rows,
+           int64_t qt_gstride, int64_t st_gstride, uintptr_t stream) {
+          MxQuantTGroupedArgs a;
+          a.x = (const void*)x; a.qt = (void*)qt; a.st = (uint8_t*)st;
+          a.offs = (const int*)offs;
+          a.ngroups = ngroups;
+          a.ldx = ldx; a.ldqt = ldqt; a.ldst = ldst;
+          a.T = T; a.C = C;
+          a.stacked_rows = stacked_rows;
+          a.qt_gstride = qt_gstride; a.st_gstride = st_gstride;
+          check(mx_quantize_t_grouped_launch(a, din, fp4, (hipStream_t)stream),
+                "mx_quantize_t_grouped");
+        },
+        py::arg("x"), py::arg("qt"), py::arg("st"), py::arg("offs"), py::arg("ngroups"),
+        py::arg("ldx"), py::arg("ldqt"), py::arg("ldst"), py::arg("T"), py::arg("C"),
+        py::arg("din"), py::arg("fp4") = false, py::arg("stacked_rows") = 0,
+        py::arg("qt_gstride") = 0, py::arg("st_gstride") = 0, py::arg("stream") = 0);
   // x[R, K] f32 / f16 / bf16 -> q[R, K] e4m3 + s[R, K / 32] E8M0 bytes; mxfp4_quantize: the same
   // -> q[R, K / 2] E2M1 nibble pairs (ldq in bytes) + s
   def_row_quantizer(m, "mx_quantize", mx_quantize_launch);

@@ -210,6 +210,18 @@ struct GemmArgs {
   const int* grp_offs = nullptr;
   int ngroups = 0;
   int64_t b_gstride = 0, b_scale_gstride = 0;
+  // K-grouped form (optional; grp_offs / ngroups as above, block-scaled fp8 / fp4 operands, codes
+  // of mxs_offers(), dense output): the groups lie along the CONTRACTION axis. With the offsets
+  // clamped to kgrp_rows (T) as above, n_g = o'[g + 1] - o'[g] and MOD = 128 (fp4: 256) elements,
+  // group g owns columns [k0_g, k0_g + kl_g) of a, b and (over 32) of both scale arrays,
+  //   kl_g = MOD ceil(n_g / MOD),  k0_g = MOD sum_{j < g} ceil(n_j / MOD)   (tile_map.h),
+  // and writes c + g * c_kgstride ELEMENTS: c[g] = a[:, cols g] b[:, cols g]^T, [M, N] with rows
+  // ldc apart; a group without columns writes +0.0. K is the operands' column extent and is at
+  // least kgrouped_capacity(T, ngroups, MOD), so no content of the offsets addresses a column
+  // outside it. M and N are the ordinary extents of a and b here. The wgrad of a routed layer.
+  int kgrouped = 0;
+  int kgrp_rows = 0;
+  int64_t c_kgstride = 0;
 };
 constexpr int kMaxGroups = 1024;
 // The byte view of a launch whose operands and / or output are fp4: the kernels address bytes (two
@@ -271,6 +283,29 @@ struct MxQuantTArgs {
 };
 hipError_t mx_quantize_t_launch(const MxQuantTArgs& a, int din, bool fp4, bool two,
                                 hipStream_t s);
+
+// Grouped transposing MX quantiser (csrc/gemm/mx_quant_t_grouped.hip): x[T, C], the rows sorted
+// into ngroups groups by the DEVICE array offs (ngroups + 1 int32, clamped to T as a grouped GEMM
+// clamps them, read by the kernel only) -> qt[C, cap] (fp4: [C, cap / 2]) and st[C, cap / 32],
+// cap = kgrouped_capacity(T, ngroups, MOD), MOD = 128 (fp4: 256): columns [k0_g, k0_g + kl_g) of
+// row c hold the blocks of x[o'[g] : o'[g + 1], c], zero-extended to kl_g rows (tile_map.h
+// kgrouped_range has the layout), i.e. mx_quantize_t_launch of the group's rows padded with zero
+// rows, byte for byte: the operands of a K-grouped GEMM. Columns at or past k0_E are not written.
+// stacked_rows = R > 0 (R % MOD == 0): group g goes to the slab qt + g * qt_gstride /
+// st + g * st_gstride BYTES instead, from column 0 of the slab, [C, R] / [C, R / 32]; a tile of
+// the group at or past row R is dropped. Alignment as for mx_quantize_t_launch; ldqt / ldst hold
+// the capacity (stacked: R); 1 <= ngroups <= kMaxGroups. T == 0 or C == 0 launches nothing.
+struct MxQuantTGroupedArgs {
+  const void* x = nullptr;
+  void* qt = nullptr;
+  uint8_t* st = nullptr;
+  const int* offs = nullptr;
+  int64_t ldx = 0, ldqt = 0, ldst = 0;
+  int64_t qt_gstride = 0, st_gstride = 0;
+  int T = 0, C = 0, ngroups = 0, stacked_rows = 0;
+};
+hipError_t mx_quantize_t_grouped_launch(const MxQuantTGroupedArgs& a, int din, bool fp4,
+                                        hipStream_t s);
 
 hipError_t gemm_launch(const GemmArgs& p, int din, int dout, int tile, int mode, hipStream_t s);
 bool gemm_fast_path_ok(const GemmArgs& p, int din, int dout);

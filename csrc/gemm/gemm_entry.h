@@ -38,6 +38,13 @@ hipError_t launch_grouped_bf16_q(const GemmArgs& p, int dout, int tile, hipStrea
 hipError_t launch_grouped_f16_q(const GemmArgs& p, int dout, int tile, hipStream_t s);
 hipError_t launch_grouped_mxs_q(const GemmArgs& p, int dout, int tile, hipStream_t s);
 hipError_t launch_grouped_mx4_q(const GemmArgs& p, int dout, int tile, hipStream_t s);
+// K-grouped launches (GemmArgs::kgrouped): gemm_launch calls launch_kgrouped (gemm_kgrouped.hip),
+// which picks the translation unit by operands (fp8 / fp4 with scales: gemm_kgrouped_<in>.hip).
+// Weak for the same reason as launch_grouped.
+hipError_t launch_kgrouped(const GemmArgs& p, int din, int dout, int tile, hipStream_t s)
+    __attribute__((weak));
+hipError_t launch_kgrouped_mxs(const GemmArgs& p, int dout, int tile, hipStream_t s);
+hipError_t launch_kgrouped_mx4(const GemmArgs& p, int dout, int tile, hipStream_t s);
 
 // Dispatch of the fast (MFMA) family by dtype pair; hipErrorInvalidValue if not provided.
 inline hipError_t launch_fast(const GemmArgs& p, int din, int dout, int tile, hipStream_t s) {

@@ -1,0 +1,11 @@
+// gemm_kgrouped_mxs: the K-grouped form of the tiled kernel (GemmArgs::kgrouped;
+// gemm_tn_kgrouped_kernel, gemm_kgrouped_kernels.h), the four codes of mxs_offers():
+// block-scaled fp8 operands, bf16 / f16 / f32 out.
+#include "gemm_kgrouped_kernels.h"
+#include "gemm_entry.h"
+
+namespace ddlb {
+hipError_t launch_kgrouped_mxs(const GemmArgs& p, int dout, int tile, hipStream_t s) {
+  return launch_kgrouped_t<MmaMXS>(p, dout, tile, s);
+}
+}  // namespace ddlb

@@ -291,6 +291,50 @@ static hipError_t gemm_launch_grouped_dense(const GemmArgs& p, int din, int dout
   return launch_grouped_checked(p, din, dout, tile, s);
 }
 
+// K-grouped launches (GemmArgs::kgrouped): the K-grouped tiled kernel or hipErrorInvalidValue. The
+// offsets are device memory and are never read here. What the M-grouped form refuses about flags,
+// tables, grouped rows, K-split, all-gather, tile codes and the number of groups is refused here
+// too, and so are an activation, a gate, a quantised output and unscaled operands. K is the
+// operands' column extent: whole K-tiles, at least the capacity of (T, E, MOD), so no content of
+// the offsets reaches a column outside an operand row (tile_map.h); rows and scales as the scaled
+// flavour it runs asks for them. The groups' outputs lie c_kgstride elements apart without
+// overlap, 8-byte aligned as c is.
+static hipError_t gemm_launch_kgrouped(const GemmArgs& p, int din, int dout, int tile, int mode,
+                                       hipStream_t s) {
+  const bool in4 = din == DT_FP4;
+  const int MOD = in4 ? 256 : 128;
+  if (p.grp_offs == nullptr || p.ngroups <= 0 || p.ngroups > kMaxGroups)
+    return hipErrorInvalidValue;
+  if (din != DT_FP8 && !in4) return hipErrorInvalidValue;
+  if (p.a_scale == nullptr || p.b_scale == nullptr) return hipErrorInvalidValue;
+  if (dout != DT_F32 && dout != DT_BF16 && dout != DT_F16) return hipErrorInvalidValue;
+  if (p.act != ACT_NONE || p.glu || p.c_scale != nullptr) return hipErrorInvalidValue;
+  if (mode != GEMM_MODE_AUTO && mode != GEMM_MODE_MX) return hipErrorInvalidValue;
+  if (tile != TILE_AUTO && !mxs_offers(tile)) return hipErrorInvalidValue;
+  if (p.b_gstride != 0 || p.b_scale_gstride != 0) return hipErrorInvalidValue;
+  if (p.M < 0 || p.N < 0 || p.K <= 0 || p.K % MOD || p.kgrp_rows < 0)
+    return hipErrorInvalidValue;
+  const hipError_t e = plain_operands_only(p, true, true, hipErrorInvalidValue);
+  if (e != hipSuccess) return e;
+  if (p.K < kgrouped_capacity(p.kgrp_rows, p.ngroups, MOD)) return hipErrorInvalidValue;
+  if (p.M == 0 || p.N == 0) return hipSuccess;
+  if (in4 && (p.lda % 2 || p.ldb % 2)) return hipErrorInvalidValue;
+  if (p.a == nullptr || p.b == nullptr || p.c == nullptr || p.lda < p.K || p.ldb < p.K ||
+      p.ldc < p.N || !gemm_fast_path_ok(fp4_byte_view(p, in4, false), in4 ? DT_U8 : din, dout))
+    return hipErrorInvalidValue;
+  if (!scale_operands_ok(p, in4 ? 8 : 4)) return hipErrorInvalidValue;
+  if (p.c_kgstride < 0 || p.c_kgstride * dtype_size(dout) % 8 ||
+      (p.ngroups > 1 && p.c_kgstride < (int64_t)p.M * p.ldc))
+    return hipErrorInvalidValue;
+  if (tile == TILE_AUTO) tile = mxs_tile_for(choose_tile(p.M, p.N, p.K, din));
+  if (tile < 0) return hipErrorInvalidValue;
+  const int64_t tiles = (int64_t)((p.M + tile_rows(tile) - 1) / tile_rows(tile)) *
+                        ((p.N + tile_cols(tile) - 1) / tile_cols(tile));
+  if (tiles * p.ngroups > 0x7FFFFFFFLL) return hipErrorInvalidValue;
+  if (launch_kgrouped == nullptr) return hipErrorNotSupported;
+  return launch_kgrouped(p, din, dout, tile, s);
+}
+
 hipError_t gemm_launch(const GemmArgs& p_in, int din, int dout, int tile, int mode,
                        hipStream_t s) {
   GemmArgs p = p_in;
@@ -298,6 +342,7 @@ hipError_t gemm_launch(const GemmArgs& p_in, int din, int dout, int tile, int mo
   if (p.c_grp <= 0) { p.c_grp = p.M > 0 ? p.M : 1; p.c_gstride = p.c_grp; }
   // known codes only (the retired families' codes are refused, not rerouted)
   if (tile != TILE_AUTO && tile_slot(tile) < 0) return hipErrorInvalidValue;
+  if (p.kgrouped) return gemm_launch_kgrouped(p, din, dout, tile, mode, s);
   const bool grouped = grouped_launch(p);
   if (grouped) {
     const hipError_t e = grouped_operands_ok(p, din, tile, mode);

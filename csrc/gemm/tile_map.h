@@ -136,6 +136,48 @@ __host__ __device__ inline bool grouped_tile(const int* offs, int T, int E, int 
   return found;
 }
 
+// ---------------------------------------------------------------- K-grouped GEMM (kgrouped)
+// The padded layout of a contraction axis that is cut into groups (the wgrad of a routed layer
+// contracts the rows of a group): group g, n_g = o'[g + 1] - o'[g] rows, owns the columns
+//   [k0_g, k0_g + kl_g),  kl_g = MOD ceil(n_g / MOD),  k0_g = MOD sum_{j < g} ceil(n_j / MOD),
+// MOD being the scaled kernels' K-tile in elements (128, fp4: 256) and the grouped transposing
+// quantiser's tile rows. k0_g / MOD is the launch-wide m-tile index grouped_tile numbers with
+// BM = MOD, so the quantiser (which writes the layout) and the GEMM (which reads it) both derive
+// it from the raw offsets. By the bound of grouped_grid_bound, k0_E <= (T / MOD + E) MOD:
+__host__ __device__ inline int64_t kgrouped_capacity(int T, int E, int MOD) {
+  return ((int64_t)(T / MOD) + E) * MOD;
+}
+
+// Group g -> its column range. The scan reads the offsets eight at a time as grouped_tile does
+// (an index past E re-reads o[E]) and stops after the chunk that holds g. The range is clamped
+// against the capacity as well: whatever the array holds, k0 + kl <= kgrouped_capacity(T, E, MOD).
+// g outside [0, E) gives an empty range at k0_E.
+__host__ __device__ inline void kgrouped_range(const int* offs, int T, int E, int MOD, int g,
+                                               int64_t& k0, int64_t& kl) {
+  int lo = grouped_clamp(offs[0], 0, T);
+  int64_t acc = 0, len = 0;
+  bool found = false;
+  for (int g0 = 0; g0 < E && !found; g0 += 8) {
+    int o[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = offs[g0 + j + 1 < E ? g0 + j + 1 : E];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int hi = grouped_clamp(o[j], lo, T);
+      const int nt = (hi - lo) / MOD + ((hi - lo) % MOD != 0);
+      if (g0 + j == g) {
+        found = true;
+        len = nt;
+      }
+      if (!found) acc += nt;
+      lo = hi;
+    }
+  }
+  const int64_t cap = kgrouped_capacity(T, E, MOD);
+  k0 = acc * MOD < cap ? acc * MOD : cap;
+  kl = len * MOD < cap - k0 ? len * MOD : cap - k0;
+}
+
 // In-kernel all-gather work unit u -> (block b, producer prod, part pi): block-major; within a
 // block, consecutive units go to different producers (ring order from rank + 1), so the copy
 // workgroups in flight spread over every peer / xGMI link.

@@ -933,3 +933,144 @@ def gemm_grouped(a, w, offsets, out=None, *, out_dtype=None, tile: str = "auto",
         if out_scale is not None:
             out_scale.record_stream(torch.cuda.ExternalStream(s))
     return out if out_quant is None else (out[:T], out_scale[:T])
+
+
+# ---------------------------------------------------------------- K-grouped GEMM (routed wgrad)
+def kgrouped_capacity(T: int, E: int, mod: int) -> int:
+    """Columns that hold the padded K layout of any ``E`` groups over ``T`` rows (tile_map.h
+    ``kgrouped_capacity``): ``(T // mod + E) * mod``, ``mod`` = 128 for MX-fp8 and 256 for MXFP4."""
+    return (int(T) // mod + int(E)) * mod
+
+
+def padded_offsets(offsets, T: int, mod: int):
+    """The padded K layout as a Python list ``k0`` of ``E + 1`` column offsets (reads the tensor on
+    the host; the kernels derive the same numbers from the raw offsets, tile_map.h
+    ``kgrouped_range``): with the offsets clamped by :func:`clamp_offsets` and ``n_g`` rows in
+    group ``g``, ``k0[g + 1] - k0[g] = mod * ceil(n_g / mod)`` and ``k0[0] = 0``. Group ``g`` owns
+    the columns ``[k0[g], k0[g + 1])``; ``k0[E] <= kgrouped_capacity(T, E, mod)``."""
+    o = clamp_offsets(offsets, T)
+    k0 = [0]
+    for g in range(len(o) - 1):
+        k0.append(k0[-1] + mod * -(-(o[g + 1] - o[g]) // mod))
+    return k0
+
+
+def _check_kgrouped(a, w, offsets, rows, out=None, *, a_scale=None, w_scale=None, out_dtype=None,
+                    tile: str = "auto"):
+    """Every refusal of the K-grouped GEMM, on the host and before anything is loaded or launched
+    (CPU tensors pass through it; the offsets' content is never read). Returns
+    ``(M, N, K, E, output dtype)``: ``K`` the operands' column extent in elements."""
+    import torch
+
+    if not isinstance(a, torch.Tensor) or not isinstance(w, torch.Tensor) or a.dim() != 2 \
+            or w.dim() != 2:
+        raise ValueError("a K-grouped GEMM takes a as [M, cap] and w as [N, cap] (2-D)")
+    fp4 = _is_fp4(a) or _is_fp4(w)
+    fp8 = a.dtype == torch.float8_e4m3fn or w.dtype == torch.float8_e4m3fn
+    if not fp4 and not fp8:
+        raise TypeError(f"a K-grouped GEMM takes block-scaled fp8 or fp4 operands, not {a.dtype}")
+    if a.dtype != w.dtype:
+        raise TypeError(f"A dtype {a.dtype} != W dtype {w.dtype}")
+    if a_scale is None or w_scale is None:
+        raise ValueError("a K-grouped GEMM needs a_scale and w_scale (the unit-scale kernels have "
+                         "no K-grouped form)")
+    if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int32:
+        raise TypeError(f"offsets must be an int32 tensor, not "
+                        f"{getattr(offsets, 'dtype', type(offsets))}")
+    if offsets.dim() != 1 or not offsets.is_contiguous():
+        raise ValueError(f"offsets must be contiguous and 1-D, not {tuple(offsets.shape)}")
+    E = offsets.shape[0] - 1
+    if E < 1:
+        raise ValueError("a K-grouped GEMM needs at least one group")
+    if E > MAX_GROUPS:
+        raise ValueError(f"a K-grouped GEMM takes at most {MAX_GROUPS} groups, not {E}")
+    if offsets.device != a.device or w.device != a.device:
+        raise ValueError("operands and offsets on different devices")
+    if not isinstance(rows, int) or isinstance(rows, bool) or rows < 0 or rows >= 2 ** 31:
+        raise ValueError(f"rows (the bound the offsets are clamped to) must be an int in "
+                         f"[0, 2^31), not {rows!r}")
+    if tile != "auto" and tile not in SCALED_TILES:
+        raise ValueError(f"a K-grouped GEMM is offered for tile auto / {SCALED_TILES}, not "
+                         f"{tile!r}")
+    f = _MX_FP4 if fp4 else _MX_FP8
+    M, N = a.shape[0], w.shape[0]
+    K = f.per_byte * a.shape[1]
+    if a.shape[1] != w.shape[1]:
+        raise ValueError(f"K mismatch: A {tuple(a.shape)} vs W {tuple(w.shape)}")
+    if M >= 2 ** 31 or N >= 2 ** 31 or K >= 2 ** 31:
+        raise ValueError("dimensions must fit in 32 bits")
+    cap = kgrouped_capacity(rows, E, f.kmod)
+    if K < cap:
+        raise ValueError(f"the operands have {K} columns, below the capacity {cap} of the padded "
+                         f"layout of {E} groups over {rows} rows")
+    for name, t in (("a", a), ("w", w)):
+        if t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+            raise ValueError(f"{name} needs unit inner stride (strides {tuple(t.stride())})")
+    _check_block_scaled(f, a, w, a_scale, w_scale, M, tile, "auto", 0, 0)
+    dense = (torch.bfloat16, torch.float16, torch.float32)
+    odt = out.dtype if out is not None else (out_dtype or torch.bfloat16)
+    if out is not None and out_dtype is not None and out_dtype != out.dtype:
+        raise TypeError(f"out is {out.dtype}, out_dtype={out_dtype}")
+    if odt not in dense:
+        raise TypeError(f"a K-grouped GEMM writes one of {dense}, not {odt}")
+    if out is not None:
+        if out.device != a.device:
+            raise ValueError(f"out is on {out.device}, the operands on {a.device}")
+        if out.dim() != 3 or tuple(out.shape) != (E, M, N):
+            raise ValueError(f"out must have shape {(E, M, N)}, not {tuple(out.shape)}")
+        if out.stride(2) != 1 or out.stride(1) < N or \
+                (E > 1 and out.stride(0) < M * out.stride(1)):
+            raise ValueError(f"out needs unit inner stride, rows of at least N and groups at "
+                             f"least M rows apart (strides {tuple(out.stride())})")
+        if out.stride(0) * out.element_size() % 8:
+            raise ValueError("the groups' outputs must be a multiple of 8 bytes apart")
+    return M, N, K, E, odt
+
+
+def gemm_kgrouped(a, w, offsets, rows, out=None, *, a_scale, w_scale, out_dtype=None,
+                  tile: str = "auto", stream=None):
+    """K-grouped GEMM in ONE launch, the wgrad of a routed linear layer: the groups lie along the
+    contraction axis and each writes its own matrix,
+    ``out[g] = a[:, k0_g : k0_g + kl_g] @ w[:, k0_g : k0_g + kl_g].T`` under the block scales of
+    the same columns. ``a [M, cap]`` and ``w [N, cap]`` are block-scaled fp8 or fp4 in the padded
+    K layout :func:`ddlb_amd.ops.mx.quantize_mx_t_grouped` writes (``a_scale [M, cap / 32]``,
+    ``w_scale [N, cap / 32]``; ``cap >= kgrouped_capacity(rows, E, 128 | 256)``); ``offsets`` is
+    the int32 ``[E + 1]`` device tensor of row offsets that only the kernel reads, clamped to
+    ``rows`` (``T``) as everywhere (:func:`clamp_offsets`), and :func:`padded_offsets` gives the
+    column ranges the kernel derives from it. No host sync; nothing in ``offsets`` can address a
+    column outside the operands.
+
+    ``out [E, M, N]`` bf16 (default) / f16 / f32, ``out.stride(0) >= M * out.stride(1)``; every
+    ``out[g]`` is bit for bit what ``gemm`` with the same tile writes for those column slices, and
+    a group without rows gets ``+0.0`` everywhere. Tiles :data:`SCALED_TILES`.
+    :func:`_check_kgrouped` holds every refusal."""
+    import torch
+
+    M, N, K, E, odt = _check_kgrouped(a, w, offsets, rows, out, a_scale=a_scale, w_scale=w_scale,
+                                      out_dtype=out_dtype, tile=tile)
+    C = load()
+    _check_placement(a)
+    if w.device.type != "cuda":
+        raise ValueError("native GEMM operands must be ROCm device tensors")
+    if out is None:
+        out = torch.empty((E, M, N), dtype=odt, device=a.device)
+    _check_placement(out[0])
+    fp4 = _is_fp4(a)
+    if M and N and not C.gemm_fast_path_ok(a.data_ptr(), w.data_ptr(), out.data_ptr(),
+                                           a.stride(0), w.stride(0), out.stride(1), M, N,
+                                           K // 2 if fp4 else K,
+                                           DT_U8 if fp4 else dtype_code(a.dtype),
+                                           dtype_code(odt)):
+        raise ValueError("a K-grouped GEMM needs the MFMA fast path: 16-byte-aligned operand "
+                         "rows, 8-byte-aligned output rows")
+    s = stream if stream is not None else torch.cuda.current_stream(a.device).cuda_stream
+    am = 2 if fp4 else 1
+    C.gemm_kgrouped(
+        a=a.data_ptr(), b=w.data_ptr(), c=out.data_ptr(), offs=offsets.data_ptr(), ngroups=E,
+        rows=rows, lda=am * a.stride(0), ldb=am * w.stride(0), ldc=out.stride(1),
+        c_gstride=out.stride(0), M=M, N=N, K=K, din=DT_FP4 if fp4 else dtype_code(a.dtype),
+        dout=dtype_code(odt), tile=TILES[tile], stream=s, a_scale=a_scale.data_ptr(),
+        b_scale=w_scale.data_ptr(), a_scale_ld=a_scale.stride(0), b_scale_ld=w_scale.stride(0))
+    if stream is not None:  # the output stays allocated until that stream reaches it
+        out.record_stream(torch.cuda.ExternalStream(s))
+    return out

@@ -405,3 +405,182 @@ def quantize_mx_2way(x, *, fmt: str = "mx", stream=None):
     qt, st = _alloc_quant(C, R, fp4, x.device)
     _launch_quant_t(x, R, C, fp4, qt, st, q, s, stream)
     return q.view(qdt), s, qt.view(qdt), st
+
+
+# ---------------------------------------------------------------- grouped transposing quantiser
+# The operands of a K-grouped GEMM (ddlb_amd.ops.gemm.gemm_kgrouped): the rows of x are sorted into
+# groups and every group is quantised down its own rows, its blocks starting at the group's first
+# row and its tail padded with zeros to a whole K-tile (ops.gemm.padded_offsets has the layout).
+def quantize_mx_t_grouped_reference(x, offsets, fmt: str = "mx", stacked_rows: int = 0):
+    """The specification of :func:`quantize_mx_t_grouped` on any device (reads ``offsets`` on the
+    host): per group, :func:`quantize_mx_t_reference` of the group's rows padded with zero rows to
+    a multiple of 128 (``fmt="mxfp4"``: 256). Returns ``(qt, st, written)`` as uint8 tensors:
+    ``qt [C, cap]`` (fp4 ``[C, cap / 2]``), ``st [C, cap / 32]`` and a bool ``[cap]`` that marks
+    the columns some group owns (the others hold zeros here and are not written by the kernel).
+    ``stacked_rows = R``: ``qt [E, C, R]`` (fp4 ``R / 2``), ``st [E, C, R / 32]``, ``written
+    [E, R]``; a group's tiles at or past row ``R`` are dropped."""
+    import torch
+
+    from ddlb_amd.ops.gemm import clamp_offsets, kgrouped_capacity, padded_offsets
+
+    fp4 = _t_fmt(fmt)
+    mod = 256 if fp4 else 128
+    T, C = x.shape
+    E = offsets.shape[0] - 1
+    o = clamp_offsets(offsets, T)
+    R = int(stacked_rows)
+    cap = R if R else kgrouped_capacity(T, E, mod)
+    lead = (E,) if R else ()
+    qt = torch.zeros(lead + (C, cap // 2 if fp4 else cap), dtype=torch.uint8, device=x.device)
+    st = torch.zeros(lead + (C, cap // BLOCK), dtype=torch.uint8, device=x.device)
+    written = torch.zeros(lead + (cap,), dtype=torch.bool, device=x.device)
+    k0s = padded_offsets(offsets, T, mod)
+    for g in range(E):
+        n = o[g + 1] - o[g]
+        kl = k0s[g + 1] - k0s[g]
+        if kl == 0:
+            continue
+        pad = torch.zeros((kl, C), dtype=x.dtype, device=x.device)
+        pad[:n] = x[o[g]:o[g + 1]]
+        q, s = quantize_mx_t_reference(pad, fmt)
+        q = q.view(torch.uint8)
+        if R:
+            kl = min(kl, R)
+            qt[g, :, :kl // (2 if fp4 else 1)] = q[:, :kl // (2 if fp4 else 1)]
+            st[g, :, :kl // BLOCK] = s[:, :kl // BLOCK]
+            written[g, :kl] = True
+        else:
+            k0 = k0s[g]
+            d = 2 if fp4 else 1
+            qt[:, k0 // d:(k0 + kl) // d] = q
+            st[:, k0 // BLOCK:(k0 + kl) // BLOCK] = s
+            written[k0:k0 + kl] = True
+    return qt, st, written
+
+
+def _check_quant_t_grouped(x, offsets, fmt: str, out=None, stacked_rows: int = 0):
+    """Every refusal of :func:`quantize_mx_t_grouped`, on the host and before the extension is
+    loaded (CPU tensors reach the device refusal; the offsets' content is never read). Returns
+    ``(T, C, E, fp4, cap)``: ``cap`` the column capacity of the outputs (stacked: ``R``)."""
+    import torch
+
+    from ddlb_amd.ops.gemm import MAX_GROUPS, kgrouped_capacity
+
+    name = "quantize_mx_t_grouped"
+    fp4 = _t_fmt(fmt)
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{name} expects a tensor")
+    if x.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+        raise TypeError(f"{name} takes {IN_DTYPES}, not {x.dtype}")
+    if fp4 and not hasattr(torch, "float4_e2m1fn_x2"):
+        raise TypeError("fmt='mxfp4' needs torch.float4_e2m1fn_x2")
+    if x.dim() != 2:
+        raise ValueError(f"{name} expects a 2-D tensor, not {tuple(x.shape)}")
+    if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int32:
+        raise TypeError(f"offsets must be an int32 tensor, not "
+                        f"{getattr(offsets, 'dtype', type(offsets))}")
+    if offsets.dim() != 1 or not offsets.is_contiguous():
+        raise ValueError(f"offsets must be contiguous and 1-D, not {tuple(offsets.shape)}")
+    E = offsets.shape[0] - 1
+    if E < 1 or E > MAX_GROUPS:
+        raise ValueError(f"{name} takes 1 .. {MAX_GROUPS} groups (offsets of 2 .. "
+                         f"{MAX_GROUPS + 1} entries), not {E}")
+    if offsets.device != x.device:
+        raise ValueError(f"offsets is on {offsets.device}, x on {x.device}")
+    T, C = x.shape
+    mod = 256 if fp4 else 128
+    R = int(stacked_rows)
+    if R < 0 or R % mod:
+        raise ValueError(f"{name}(fmt={fmt!r}) needs stacked_rows % {mod} == 0 and >= 0, not {R}")
+    if (C * x.element_size()) % 16:
+        raise ValueError(f"{name} needs rows of whole 16-byte vectors (x is {T} x {C} {x.dtype})")
+    if T >= 2 ** 31 or C >= 2 ** 31:
+        raise ValueError("dimensions must fit in 32 bits")
+    empty = T == 0 or C == 0
+    if not empty and (x.stride(1) != 1 or (T > 1 and x.stride(0) < C)):
+        raise ValueError(f"{name} needs row-major input with unit inner stride")
+    if not empty and (x.data_ptr() % 16 or (x.stride(0) * x.element_size()) % 16):
+        raise ValueError(f"{name} needs 16-byte-aligned rows")
+    cap = R if R else kgrouped_capacity(T, E, mod)
+    ctiles = (C + 63) // 64
+    if min(T // mod + E, -(-T // mod) * E) * ctiles > 2 ** 31 - 1:
+        raise ValueError(f"{name}: the grid bound does not fit a launch")
+    ncol, sal = (cap // 2 if fp4 else cap), (8 if fp4 else 4)
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise TypeError("out must be a pair (qt, st)")
+        qt, st = out
+        qdt = torch.float4_e2m1fn_x2 if fp4 else torch.float8_e4m3fn
+        check_quant_pair_types(("out[0]", "out[1]"), qt, st, qdt, f"fmt={fmt!r}")
+        if qt.device != x.device or st.device != x.device:
+            raise ValueError(f"out is on {qt.device} / {st.device}, x on {x.device}")
+        lead = (E,) if R else ()
+        if tuple(qt.shape) != lead + (C, ncol):
+            raise ValueError(f"out[0] must have shape {lead + (C, ncol)}, not {tuple(qt.shape)}")
+        if tuple(st.shape) != lead + (C, cap // BLOCK):
+            raise ValueError(f"out[1] must have shape {lead + (C, cap // BLOCK)}, not "
+                             f"{tuple(st.shape)}")
+        if R:
+            for nm, t, m in (("out[0]", qt, 16), ("out[1]", st, sal)):
+                if t.stride(0) % m or (E > 1 and t.stride(0) < C * t.stride(1)):
+                    raise ValueError(f"{nm} needs slabs a multiple of {m} bytes and at least C "
+                                     f"rows apart (strides {tuple(t.stride())})")
+            check_quant_pair_layout(("out[0]", "out[1]"), qt[0], st[0], ncol, cap // BLOCK, sal)
+        else:
+            check_quant_pair_layout(("out[0]", "out[1]"), qt, st, ncol, cap // BLOCK, sal)
+    if x.device.type != "cuda":  # last, so that CPU tensors reach every refusal above
+        raise ValueError(f"{name} needs a ROCm device tensor (quantize_mx_t_grouped_reference "
+                         "runs anywhere)")
+    return T, C, E, fp4, cap
+
+
+def quantize_mx_t_grouped(x, offsets, *, fmt: str = "mx", out=None, stacked_rows: int = 0,
+                          stream=None):
+    """The HIP grouped transposing quantiser (``csrc/gemm/mx_quant_t_grouped.hip``): ``x [T, C]``
+    bf16 / f16 / f32 with its rows sorted into ``E`` groups by ``offsets`` (int32 ``[E + 1]`` on
+    ``x``'s device, read by the kernel only and clamped as a grouped GEMM clamps them: no host
+    sync) -> ``(qt, st)`` in the padded K layout of :func:`ddlb_amd.ops.gemm.gemm_kgrouped`:
+    ``qt [C, cap]`` float8_e4m3fn (``fmt="mxfp4"``: ``[C, cap / 2]`` float4_e2m1fn_x2) and
+    ``st [C, cap / 32]`` uint8, ``cap = kgrouped_capacity(T, E, 128 | 256)``. Group ``g``'s columns
+    ``[k0_g, k0_g + kl_g)`` (:func:`ddlb_amd.ops.gemm.padded_offsets`) hold, byte for byte,
+    :func:`quantize_mx_t_reference` of the group's rows padded with zero rows; columns at or past
+    ``k0_E`` are not written (and unspecified in outputs allocated here).
+
+    ``stacked_rows = R > 0`` (a multiple of 128 | 256): group ``g`` is written to ``qt[g]`` of
+    ``qt [E, C, R]`` / ``st [E, C, R / 32]`` from column 0 and its tiles at or past row ``R`` are
+    dropped. With ``x = w.reshape(E * N, K)``, ``offsets = arange(E + 1) * N`` and ``R = N`` one
+    launch gives the column-wise quantisation ``[E, K, N]`` of every expert's weight, the ``w`` /
+    ``w_scale`` a grouped dgrad takes.
+
+    ``out = (qt, st)`` may be preallocated (aligned as for :func:`quantize_mx_t`).
+    :func:`_check_quant_t_grouped` holds every refusal."""
+    import torch
+
+    from ddlb_amd.ops import load
+    from ddlb_amd.ops.gemm import dtype_code
+
+    T, C, E, fp4, cap = _check_quant_t_grouped(x, offsets, fmt, out, stacked_rows)
+    R = int(stacked_rows)
+    qdt = torch.float4_e2m1fn_x2 if fp4 else torch.float8_e4m3fn
+    if out is None:
+        lead = (E,) if R else ()
+        qt = torch.empty(lead + (C, cap // 2 if fp4 else cap), dtype=torch.uint8,
+                         device=x.device).view(qdt)
+        st = torch.empty(lead + (C, cap // BLOCK), dtype=torch.uint8, device=x.device)
+    else:
+        qt, st = out
+    C_ = load()
+    if T == 0 or C == 0:
+        return qt, st
+    strm = stream if stream is not None else torch.cuda.current_stream(x.device).cuda_stream
+    with torch.cuda.device(x.device):
+        C_.mx_quantize_t_grouped(
+            x=x.data_ptr(), qt=qt.data_ptr(), st=st.data_ptr(), offs=offsets.data_ptr(),
+            ngroups=E, ldx=max(x.stride(0), C), ldqt=qt.stride(-2), ldst=st.stride(-2), T=T, C=C,
+            din=dtype_code(x.dtype), fp4=fp4, stacked_rows=R,
+            qt_gstride=qt.stride(0) if R else 0, st_gstride=st.stride(0) if R else 0,
+            stream=strm)
+    if stream is not None:  # the outputs stay allocated until that stream reaches them
+        for t in (qt, st):
+            t.record_stream(torch.cuda.ExternalStream(strm))
+    return qt, st
