@@ -15,6 +15,8 @@
 
 #include "comm/comm.h"
 #include "gemm/gemm.h"
+#include "moe/moe.h"
+#include "moe/moe_route_map.h"
 #include "runtime/kernels.h"
 #include "runtime/plan.h"
 
@@ -265,6 +267,51 @@ PYBIND11_MODULE(_C, m) {
   // -> q[R, K / 2] E2M1 nibble pairs (ldq in bytes) + s
   def_row_quantizer(m, "mx_quantize", mx_quantize_launch);
   def_row_quantizer(m, "mxfp4_quantize", mxfp4_quantize_launch);
+  m.def("mx_quantize_gather",  // q / s row r = the row quantiser's output for x[src[r]]; an index
+        // outside [0, X) gives a zero row. src is device memory, never read here.
+        [](uintptr_t x, uintptr_t src, uintptr_t q, uintptr_t sc, int64_t ldx, int64_t ldq,
+           int64_t lds, int R, int K, int X, int din, bool fp4, uintptr_t stream) {
+          MxQuantGatherArgs a;
+          a.x = (const void*)x; a.q = (void*)q; a.s = (uint8_t*)sc;
+          a.src = (const int*)src;
+          a.ldx = ldx; a.ldq = ldq; a.lds = lds;
+          a.R = R; a.K = K; a.X = X;
+          check(mx_quantize_gather_launch(a, din, fp4, (hipStream_t)stream),
+                "mx_quantize_gather");
+        },
+        py::arg("x"), py::arg("src"), py::arg("q"), py::arg("s"), py::arg("ldx"), py::arg("ldq"),
+        py::arg("lds"), py::arg("R"), py::arg("K"), py::arg("X"), py::arg("din"),
+        py::arg("fp4") = false, py::arg("stream") = 0);
+  // MoE dispatch (csrc/moe): the routing sort and the weighted un-permute. Every array is device
+  // memory that only the kernels read or write.
+  m.attr("ROUTE_CHUNK") = kRouteChunk;
+  m.def("moe_route",
+        [](uintptr_t ids, uintptr_t offsets, uintptr_t row_token, uintptr_t slot_row,
+           uintptr_t ws, int64_t n, int k, int E, bool ids64, uintptr_t stream) {
+          MoeRouteArgs a;
+          a.ids = (const void*)ids;
+          a.offsets = (int*)offsets; a.row_token = (int*)row_token; a.slot_row = (int*)slot_row;
+          a.ws = (int*)ws;
+          a.n = n; a.k = k; a.E = E;
+          a.ids64 = ids64 ? 1 : 0;
+          check(moe_route_launch(a, (hipStream_t)stream), "moe_route");
+        },
+        py::arg("ids"), py::arg("offsets"), py::arg("row_token"), py::arg("slot_row"),
+        py::arg("ws"), py::arg("n"), py::arg("k"), py::arg("E"), py::arg("ids64"),
+        py::arg("stream") = 0);
+  m.def("moe_combine",
+        [](uintptr_t y, uintptr_t slot_row, uintptr_t gate, uintptr_t out, int64_t ldy,
+           int64_t ldo, int S, int k, int T, int H, int din, int dout, uintptr_t stream) {
+          MoeCombineArgs a;
+          a.y = (const void*)y; a.slot_row = (const int*)slot_row;
+          a.gate = (const float*)gate; a.out = (void*)out;
+          a.ldy = ldy; a.ldo = ldo;
+          a.S = S; a.k = k; a.T = T; a.H = H;
+          check(moe_combine_launch(a, din, dout, (hipStream_t)stream), "moe_combine");
+        },
+        py::arg("y"), py::arg("slot_row"), py::arg("gate"), py::arg("out"), py::arg("ldy"),
+        py::arg("ldo"), py::arg("S"), py::arg("k"), py::arg("T"), py::arg("H"), py::arg("din"),
+        py::arg("dout"), py::arg("stream") = 0);
   m.def("mx_quantize_t",  // x[R, C] -> qt[C, R] (fp4: [C, R / 2]) + st[C, R / 32], blocks down
         // the columns of x; two: also the row-wise q[R, C] (fp4: [R, C / 2]) + s[R, C / 32]
         [](uintptr_t x, uintptr_t qt, uintptr_t st, int64_t ldx, int64_t ldqt, int64_t ldst,

@@ -262,6 +262,21 @@ hipError_t mx_quantize_launch(const MxQuantArgs& a, int din, hipStream_t s);
 // j; rows ldq BYTES apart, 4-byte aligned), the same scale array; the rule with 6 in place of 448
 // (e = ex - 3 if m <= 0.75 else ex - 2), ties to the even code. K % 256 == 0.
 hipError_t mxfp4_quantize_launch(const MxQuantArgs& a, int din, hipStream_t s);
+// The gathering flavour (a routed layer's dispatch): src is a DEVICE array of R int32 row indices
+// and output row r is, byte for byte, what the launches above write for row src[r] of x[X, K];
+// an index outside [0, X) gives a zero row (zero data, scale byte 127) and reads nothing, so no
+// content of src addresses outside x. Either format (fp4: q[R, K / 2]); the same alignment and
+// K % 128 (fp4: 256) rules. R == 0 launches nothing.
+struct MxQuantGatherArgs {
+  const void* x = nullptr;
+  void* q = nullptr;
+  uint8_t* s = nullptr;
+  const int* src = nullptr;
+  int64_t ldx = 0, ldq = 0, lds = 0;
+  int R = 0, K = 0, X = 0;
+};
+hipError_t mx_quantize_gather_launch(const MxQuantGatherArgs& a, int din, bool fp4,
+                                     hipStream_t s);
 
 // Transposing MX quantiser (csrc/gemm/mx_quant_t.hip): x[R, C] (rows ldx ELEMENTS apart) ->
 // qt[C, R] e4m3 (fp4: [C, R / 2] nibble pairs; rows ldqt BYTES apart) and st[C, R / 32] E8M0

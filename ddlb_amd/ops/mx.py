@@ -223,6 +223,91 @@ def quantize_mxfp4(x, *, stream=None):
     return _quantize_rows(x, True, stream)
 
 
+# ---------------------------------------------------------------- gathering quantisation
+# A routed layer quantises its tokens in the order of its sorted (token, choice) rows. The row
+# quantiser has to read x anyway, so it reads x[src[r]] and the permuted 16-bit copy of x is never
+# written. An index outside x makes a zero row, which gives padding rows a defined content.
+def quantize_mx_gather_reference(x, src, fmt: str = "mx"):
+    """``x [X, K]`` (any float dtype, any device), ``src [R]`` integer -> ``(q, s)``: the reference
+    row quantisation of ``x[src]``, a zero row (zero data, scale byte 127) where ``src[r]`` is
+    outside ``[0, X)``. The specification of :func:`quantize_mx_gather`."""
+    import torch
+
+    fp4 = _t_fmt(fmt)
+    if x.dim() != 2:
+        raise ValueError(f"MX quantisation expects a 2-D tensor, not {tuple(x.shape)}")
+    r = src.to(torch.int64)
+    valid = (r >= 0) & (r < x.shape[0])
+    if x.shape[0]:
+        rows = x.index_select(0, torch.where(valid, r, torch.zeros_like(r)))
+        rows = torch.where(valid.unsqueeze(1), rows, torch.zeros_like(rows))
+    else:
+        rows = torch.zeros((r.shape[0], x.shape[1]), dtype=x.dtype, device=x.device)
+    return quantize_mxfp4_reference(rows) if fp4 else quantize_mx_reference(rows)
+
+
+def _check_quant_gather(x, src, fmt: str):
+    """Every refusal of :func:`quantize_mx_gather`, on the host and before the extension is loaded
+    (CPU tensors reach the device refusal; the indices are never read). Returns
+    ``(X, K, R, fp4)``."""
+    import torch
+
+    name = "quantize_mx_gather"
+    fp4 = _t_fmt(fmt)
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{name} expects a tensor")
+    if x.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+        raise TypeError(f"{name} takes {IN_DTYPES}, not {x.dtype}")
+    if fp4 and not hasattr(torch, "float4_e2m1fn_x2"):
+        raise TypeError("fmt='mxfp4' needs torch.float4_e2m1fn_x2")
+    (_check_2d_fp4 if fp4 else _check_2d)(x)
+    if not isinstance(src, torch.Tensor) or src.dtype != torch.int32:
+        raise TypeError(f"src must be an int32 tensor, not {getattr(src, 'dtype', type(src))}")
+    if src.dim() != 1 or not src.is_contiguous():
+        raise ValueError(f"src must be contiguous and 1-D, not {tuple(src.shape)}")
+    if src.device != x.device:
+        raise ValueError(f"src is on {src.device}, x on {x.device}")
+    X, K = x.shape
+    R = src.shape[0]
+    if X >= 2 ** 31 or K >= 2 ** 31 or R >= 2 ** 31:
+        raise ValueError("dimensions must fit in 32 bits")
+    if X and (x.stride(1) != 1 or (X > 1 and x.stride(0) < K)):
+        raise ValueError(f"{name} needs row-major input with unit inner stride")
+    if X and (x.data_ptr() % 16 or (x.stride(0) * x.element_size()) % 16):
+        raise ValueError(f"{name} needs 16-byte-aligned rows")
+    if x.device.type != "cuda":  # last, so that CPU tensors reach every refusal above
+        raise ValueError(f"{name} needs a ROCm device tensor ({name}_reference runs anywhere)")
+    return X, K, R, fp4
+
+
+def quantize_mx_gather(x, src, *, fmt: str = "mx", stream=None):
+    """The HIP gathering row quantiser (``csrc/gemm/mx_quant.hip``): ``x [X, K]`` bf16 / f16 / f32
+    and ``src [R]`` int32 on one ROCm device -> ``(q [R, K], s [R, K / 32])`` (``fmt="mxfp4"``:
+    ``q [R, K / 2]`` float4_e2m1fn_x2) with row ``r`` byte for byte what :func:`quantize_mx` /
+    :func:`quantize_mxfp4` write for ``x[src[r]]``. ``src[r]`` outside ``[0, X)`` gives a zero
+    row with scale byte 127: nothing in ``src`` (read by the kernel only, no host sync) can
+    address outside ``x``. :func:`_check_quant_gather` holds every refusal."""
+    import torch
+
+    from ddlb_amd.ops import load
+    from ddlb_amd.ops.gemm import dtype_code
+
+    X, K, R, fp4 = _check_quant_gather(x, src, fmt)
+    C = load()
+    q, s = _alloc_quant(R, K, fp4, x.device)
+    if R > 0:
+        st = stream if stream is not None else torch.cuda.current_stream(x.device).cuda_stream
+        with torch.cuda.device(x.device):
+            C.mx_quantize_gather(x=x.data_ptr(), src=src.data_ptr(), q=q.data_ptr(),
+                                 s=s.data_ptr(), ldx=max(x.stride(0), K), ldq=q.shape[1],
+                                 lds=K // BLOCK, R=R, K=K, X=X, din=dtype_code(x.dtype), fp4=fp4,
+                                 stream=st)
+        if stream is not None:  # the outputs stay allocated until that stream reaches them
+            q.record_stream(torch.cuda.ExternalStream(st))
+            s.record_stream(torch.cuda.ExternalStream(st))
+    return q.view(torch.float4_e2m1fn_x2 if fp4 else torch.float8_e4m3fn), s
+
+
 # ---------------------------------------------------------------- transposed quantisation
 # A GEMM that contracts over the ROWS of ``x [R, C]`` (a linear layer's dgrad contracts over N,
 # its wgrad over M) needs the blocks down the columns of ``x`` and those blocks stored as
