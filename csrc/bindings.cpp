@@ -125,6 +125,17 @@ GemmArgs make_args(uintptr_t a, uintptr_t b, uintptr_t c, int64_t lda, int64_t l
   return g;
 }
 
+// The block scales of the operands and the epilogue of the three GEMM bindings (an absent scale
+// pointer is 0).
+void set_scales_epilogue(GemmArgs& g, uintptr_t a_scale, uintptr_t b_scale, int64_t a_scale_ld,
+                         int64_t b_scale_ld, uintptr_t c_scale = 0, int64_t c_scale_ld = 0,
+                         int act = ACT_NONE, int glu = 0) {
+  g.a_scale = (const uint8_t*)a_scale; g.b_scale = (const uint8_t*)b_scale;
+  g.a_scale_ld = a_scale_ld; g.b_scale_ld = b_scale_ld;
+  g.c_scale = (uint8_t*)c_scale; g.c_scale_ld = c_scale_ld;
+  g.act = act; g.glu = glu != 0;
+}
+
 // The two row-wise MX quantiser bindings: one signature, one argument block, two launchers.
 void def_row_quantizer(py::module_& m, const char* name,
                        hipError_t (*launch)(const MxQuantArgs&, int, hipStream_t)) {
@@ -166,15 +177,9 @@ PYBIND11_MODULE(_C, m) {
            uintptr_t c_scale, int64_t c_scale_ld, int glu) {
           GemmArgs g = make_args(a, b, c, lda, ldb, ldc, M, N, K, a_grp, a_gstride, c_grp,
                                  c_gstride);
-          g.act = act;
           g.ksplit = ksplit > 1 ? ksplit : 1;
-          g.a_scale = (const uint8_t*)a_scale;
-          g.b_scale = (const uint8_t*)b_scale;
-          g.a_scale_ld = a_scale_ld;
-          g.b_scale_ld = b_scale_ld;
-          g.c_scale = (uint8_t*)c_scale;
-          g.c_scale_ld = c_scale_ld;
-          g.glu = glu != 0;
+          set_scales_epilogue(g, a_scale, b_scale, a_scale_ld, b_scale_ld, c_scale, c_scale_ld,
+                              act, glu);
           check(gemm_launch(g, din, dout, tile, mode, (hipStream_t)stream), "gemm_launch");
         },
         py::arg("a"), py::arg("b"), py::arg("c"), py::arg("lda"), py::arg("ldb"), py::arg("ldc"),
@@ -196,15 +201,9 @@ PYBIND11_MODULE(_C, m) {
           g.grp_offs = (const int*)offs;
           g.ngroups = ngroups;
           g.b_gstride = b_gstride;
-          g.act = act;
-          g.a_scale = (const uint8_t*)a_scale;
-          g.b_scale = (const uint8_t*)b_scale;
-          g.a_scale_ld = a_scale_ld;
-          g.b_scale_ld = b_scale_ld;
           g.b_scale_gstride = b_scale_gstride;
-          g.c_scale = (uint8_t*)c_scale;
-          g.c_scale_ld = c_scale_ld;
-          g.glu = glu != 0;
+          set_scales_epilogue(g, a_scale, b_scale, a_scale_ld, b_scale_ld, c_scale, c_scale_ld,
+                              act, glu);
           // a null offsets pointer or ngroups = 0 must be refused, not run ungrouped
           if (offs == 0 || ngroups <= 0) check(hipErrorInvalidValue, "gemm_grouped");
           check(gemm_launch(g, din, dout, tile, GEMM_MODE_AUTO, (hipStream_t)stream),
@@ -231,10 +230,7 @@ PYBIND11_MODULE(_C, m) {
           g.kgrouped = 1;
           g.kgrp_rows = rows;
           g.c_kgstride = c_gstride;
-          g.a_scale = (const uint8_t*)a_scale;
-          g.b_scale = (const uint8_t*)b_scale;
-          g.a_scale_ld = a_scale_ld;
-          g.b_scale_ld = b_scale_ld;
+          set_scales_epilogue(g, a_scale, b_scale, a_scale_ld, b_scale_ld);
           check(gemm_launch(g, din, dout, tile, GEMM_MODE_AUTO, (hipStream_t)stream),
                 "gemm_kgrouped");
         },

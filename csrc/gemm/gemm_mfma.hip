@@ -111,228 +111,101 @@ static hipError_t plain_operands_only(const GemmArgs& p, bool plain_c_rows, bool
   return hipSuccess;
 }
 
-// Grouped launches (GemmArgs::grp_offs): what a grouped launch adds to the checks of the flavour it
-// runs (the functions below, with M = T, the rows the launch may touch). The offsets are device
-// memory and are never read here. Plain rows in the launch's own order only, the tiled kernel's
-// offered codes, no generic mode; the weights of consecutive groups b_gstride elements apart
-// without overlap and as aligned as b itself, their scales b_scale_gstride bytes apart on the
-// scale words' alignment; a grid bound (tile_map.h) that is a grid.
 static bool grouped_launch(const GemmArgs& p) { return p.grp_offs != nullptr || p.ngroups != 0; }
-static hipError_t grouped_operands_ok(const GemmArgs& p, int din, int tile, int mode) {
-  if (p.grp_offs == nullptr || p.ngroups <= 0 || p.ngroups > kMaxGroups)
-    return hipErrorInvalidValue;
-  if (din != DT_BF16 && din != DT_F16 && din != DT_FP8 && din != DT_FP4)
-    return hipErrorInvalidValue;
-  if (mode == GEMM_MODE_GENERIC || (tile != TILE_AUTO && !mxs_offers(tile)))
-    return hipErrorInvalidValue;
-  if (p.M < 0 || p.N < 0) return hipErrorInvalidValue;
-  const hipError_t e = plain_operands_only(p, true, true, hipErrorInvalidValue);
-  if (e != hipSuccess) return e;
-  const int64_t esz2 = din == DT_FP4 ? 1 : 2 * dtype_size(din);  // twice the element size
-  if (p.b_gstride < 0 || p.b_gstride * esz2 % 32 ||
-      (p.ngroups > 1 && p.b_gstride < (int64_t)p.N * p.ldb))
-    return hipErrorInvalidValue;
-  if (p.b_scale != nullptr) {
-    const int align = din == DT_FP4 ? 8 : 4;
-    if (p.b_scale_gstride < 0 || p.b_scale_gstride % align ||
-        (p.ngroups > 1 && p.b_scale_gstride < (int64_t)p.N * p.b_scale_ld))
-      return hipErrorInvalidValue;
-  }
-  if (grouped_grid_bound(p.M, p.ngroups, 128, (p.N + 127) / 128) > 0x7FFFFFFFLL)
-    return hipErrorInvalidValue;
-  return hipSuccess;
-}
-// The entry of a checked grouped launch (weak: gemm_entry.h).
-static hipError_t launch_grouped_checked(const GemmArgs& p, int din, int dout, int tile,
-                                         hipStream_t s) {
-  if (launch_grouped == nullptr) return hipErrorNotSupported;
-  return launch_grouped(p, din, dout, tile, s);
-}
 
-// DT_FP4 operands: the block-scaled MXFP4 flavour of the tiled kernel or hipErrorInvalidValue,
-// never a launch with something substituted.
-static hipError_t gemm_launch_fp4(const GemmArgs& p, int dout, int tile, int mode, hipStream_t s) {
-  if (p.a_scale == nullptr || p.b_scale == nullptr) return hipErrorInvalidValue;
-  if (dout != DT_BF16 && dout != DT_F16 && dout != DT_F32) return hipErrorInvalidValue;
-  if (mode != GEMM_MODE_AUTO && mode != GEMM_MODE_MX) return hipErrorInvalidValue;
-  if (tile != TILE_AUTO && !mx4_offers(tile)) return hipErrorInvalidValue;
-  if (p.M < 0 || p.N < 0 || p.K <= 0 || p.K % 256 || p.lda % 2 || p.ldb % 2 || p.lda < p.K ||
-      p.ldb < p.K)
-    return hipErrorInvalidValue;
-  const hipError_t e = plain_operands_only(p, false, true, hipErrorInvalidValue);
-  if (e != hipSuccess) return e;
-  if (p.M == 0 || p.N == 0) return hipSuccess;
-  // the fast path's alignment, on the operands as the byte matrices the kernel reads
-  if (p.a == nullptr || p.b == nullptr || p.c == nullptr || p.ldc < p.N ||
-      !gemm_fast_path_ok(fp4_byte_view(p, true, false), DT_U8, dout))
-    return hipErrorInvalidValue;
-  if (!scale_operands_ok(p, 8)) return hipErrorInvalidValue;
-  if (tile == TILE_AUTO) tile = mxs_tile_for(choose_tile(p.M, p.N, p.K, DT_FP4));
-  if (tile < 0) return hipErrorInvalidValue;
-  if (grouped_launch(p)) return launch_grouped_checked(p, DT_FP4, dout, tile, s);
-  return launch_fast_mx4(p, dout, tile, s);
-}
-
-// Quantised output (dout = DT_FP8 / DT_FP4 with GemmArgs::c_scale): the tiled kernel's quantising
-// epilogue or hipErrorInvalidValue, never a launch with something substituted.
-static hipError_t gemm_launch_qout(const GemmArgs& p, int din, int dout, int tile, int mode,
+// Every form of the tiled kernel beyond the plain launch, checked in one place: fp4 operands, a
+// quantised output (dout = DT_FP8 / DT_FP4 with GemmArgs::c_scale), a gated epilogue
+// (GemmArgs::glu), grouped rows (GemmArgs::grp_offs) and K-grouped columns (GemmArgs::kgrouped),
+// in any combination the kernel has. The answer is the launch of that form or
+// hipErrorInvalidValue, never a launch with something substituted (hipErrorNotSupported: a host
+// program linked without the grouped entries, gemm_entry.h). a_grp / c_grp are already defaulted
+// by gemm_launch. Offsets are device memory and are never read here.
+//  * Operands bf16 / f16 without scales, or fp8 / fp4 with both (block-scaled only); a dense
+//    output is f32 or what the operands pair with, a quantised one comes with its scales.
+//  * Plain rows in the launch's own order, the codes of mxs_offers(), mode auto (mx with scales).
+//  * Every rule on the shape comes before the empty problem's hipSuccess, every rule on pointers
+//    and layout after it: the fast path on the byte view (gemm.h fp4_byte_view), the scales, a
+//    quantised output's rows 16-byte aligned and its scales in the layout their reader takes
+//    (4-byte words; 8 for fp4 data), on cols = N / 2 columns with a gate.
+//  * Grouped: the weights of consecutive groups b_gstride elements apart without overlap and as
+//    aligned as b itself, their scales b_scale_gstride bytes apart on the scale words'
+//    alignment; a grid bound (tile_map.h) that is a grid.
+//  * K-grouped: scaled operands, a dense output, no activation or gate; K is the operands' column
+//    extent, whole K-tiles and at least the capacity of (T, E, MOD), so no content of the offsets
+//    reaches a column outside an operand row (tile_map.h); the groups' outputs lie c_kgstride
+//    elements apart without overlap, 8-byte aligned as c is.
+static hipError_t gemm_launch_form(GemmArgs p, int din, int dout, int tile, int mode,
                                    hipStream_t s) {
-  const bool q4 = dout == DT_FP4, in4 = din == DT_FP4;
-  if (p.c_scale == nullptr) return hipErrorInvalidValue;
-  if (din != DT_BF16 && din != DT_F16 && din != DT_FP8 && !in4) return hipErrorInvalidValue;
-  // fp8 / fp4 operands: block-scaled only (both scales); 16-bit operands carry none
-  const bool scaled = din == DT_FP8 || in4;
-  if (scaled ? (p.a_scale == nullptr || p.b_scale == nullptr)
-             : (p.a_scale != nullptr || p.b_scale != nullptr))
-    return hipErrorInvalidValue;
-  if (mode == GEMM_MODE_GENERIC || mode < GEMM_MODE_AUTO || mode > GEMM_MODE_MX ||
-      (!scaled && mode == GEMM_MODE_MX))
-    return hipErrorInvalidValue;
-  if (tile != TILE_AUTO && !mxs_offers(tile)) return hipErrorInvalidValue;
-  // whole 32-column blocks, as many as the GEMM that reads them takes per K-tile row
-  if (p.M < 0 || p.N < 0 || p.K <= 0 || p.N % (q4 ? 256 : 128)) return hipErrorInvalidValue;
-  const hipError_t e = plain_operands_only(p, true, true, hipErrorInvalidValue);
-  if (e != hipSuccess) return e;
-  if (p.M == 0 || p.N == 0) return hipSuccess;
-  // the fast path's alignment, on operands and output as the byte matrices the kernel touches;
-  // output rows 16-byte aligned: what the GEMM that reads them as its A asks for
-  if (in4 && (p.K % 256 || p.lda % 2 || p.ldb % 2)) return hipErrorInvalidValue;
-  if (q4 && p.ldc % 2) return hipErrorInvalidValue;
-  const GemmArgs q = fp4_byte_view(p, in4, q4);
-  if (p.a == nullptr || p.b == nullptr || p.c == nullptr || p.lda < p.K || p.ldb < p.K ||
-      p.ldc < p.N || q.ldc % 16 || ((uintptr_t)p.c & 15) ||
-      !gemm_fast_path_ok(q, in4 ? DT_U8 : din, DT_U8))
-    return hipErrorInvalidValue;
-  if (scaled && !scale_operands_ok(p, in4 ? 8 : 4)) return hipErrorInvalidValue;
-  // the output scales in the layout their reader takes (4-byte words; 8 for fp4 data)
-  const int cal = q4 ? 8 : 4;
-  if (((uintptr_t)p.c_scale & (cal - 1)) || p.c_scale_ld % cal || p.c_scale_ld < p.N / 32 ||
-      (int64_t)p.M * p.c_scale_ld >= (int64_t(1) << 31))
-    return hipErrorInvalidValue;
-  if (tile == TILE_AUTO) tile = mxs_tile_for(choose_tile(p.M, p.N, p.K, din));
-  if (tile < 0) return hipErrorInvalidValue;
-  if (grouped_launch(p)) return launch_grouped_checked(p, din, dout, tile, s);
-  return q4 ? launch_qout_fp4(p, din, tile, s) : launch_qout_fp8(p, din, tile, s);
-}
-
-// Gated (GLU) epilogue (GemmArgs::glu): the tiled kernel's offered codes, bf16 / f16 / block-scaled
-// fp8 / block-scaled fp4 operands, a dense output the operands pair with or a quantised one, plain
-// rows; or hipErrorInvalidValue, never a launch of something else. N counts the rows of b; the
-// output, its scales and every bound on them have N / 2 columns.
-static hipError_t gemm_launch_glu(const GemmArgs& p, int din, int dout, int tile, int mode,
-                                  hipStream_t s) {
+  constexpr hipError_t bad = hipErrorInvalidValue;
   const bool in4 = din == DT_FP4, scaled = din == DT_FP8 || in4;
   const bool q4 = dout == DT_FP4, qout = dout == DT_FP8 || q4;
-  if (din != DT_BF16 && din != DT_F16 && !scaled) return hipErrorInvalidValue;
-  // fp8 / fp4 operands: block-scaled only (both scales); 16-bit operands carry none
-  if (scaled ? (p.a_scale == nullptr || p.b_scale == nullptr)
-             : (p.a_scale != nullptr || p.b_scale != nullptr))
-    return hipErrorInvalidValue;
-  if (qout != (p.c_scale != nullptr)) return hipErrorInvalidValue;
+  const bool glu = p.glu != 0, kgrouped = p.kgrouped != 0;
+  const bool grouped = !kgrouped && grouped_launch(p);
+  const int64_t cols = glu ? p.N / 2 : p.N;  // of the output and, over 32, of its scales
+  const int sal = in4 ? 8 : 4, cal = q4 ? 8 : 4;
+  if (din != DT_BF16 && din != DT_F16 && !scaled) return bad;
+  if (scaled != (p.a_scale != nullptr) || scaled != (p.b_scale != nullptr)) return bad;
+  if (qout != (p.c_scale != nullptr)) return bad;
   if (!qout && dout != DT_F32 && !(scaled ? dout == DT_BF16 || dout == DT_F16 : dout == din))
-    return hipErrorInvalidValue;
-  if (mode == GEMM_MODE_GENERIC || mode < GEMM_MODE_AUTO || mode > GEMM_MODE_MX ||
-      (!scaled && mode == GEMM_MODE_MX))
-    return hipErrorInvalidValue;
-  if (tile != TILE_AUTO && !mxs_offers(tile)) return hipErrorInvalidValue;
-  // whole 64-row gate / up groups; N / 2 in whole blocks as the GEMM that reads them takes them
-  if (p.M < 0 || p.N < 0 || p.K <= 0 || p.N % (q4 ? 512 : qout ? 256 : 64))
-    return hipErrorInvalidValue;
-  const hipError_t e = plain_operands_only(p, true, true, hipErrorInvalidValue);
-  if (e != hipSuccess) return e;
-  if (p.M == 0 || p.N == 0) return hipSuccess;
-  if (in4 && (p.K % 256 || p.lda % 2 || p.ldb % 2)) return hipErrorInvalidValue;
-  if (q4 && p.ldc % 2) return hipErrorInvalidValue;
-  const GemmArgs q = fp4_byte_view(p, in4, q4);
-  if (p.a == nullptr || p.b == nullptr || p.c == nullptr || p.lda < p.K || p.ldb < p.K ||
-      p.ldc < p.N / 2 || !gemm_fast_path_ok(q, in4 ? DT_U8 : din, qout ? DT_U8 : dout))
-    return hipErrorInvalidValue;
-  if (scaled && !scale_operands_ok(p, in4 ? 8 : 4)) return hipErrorInvalidValue;
-  if (qout) {  // rows and scales as gemm_launch_qout asks for them, N / 64 scale bytes per row
-    const int cal = q4 ? 8 : 4;
-    if (q.ldc % 16 || ((uintptr_t)p.c & 15) || ((uintptr_t)p.c_scale & (cal - 1)) ||
-        p.c_scale_ld % cal || p.c_scale_ld < p.N / 64 ||
-        (int64_t)p.M * p.c_scale_ld >= (int64_t(1) << 31))
-      return hipErrorInvalidValue;
+    return bad;
+  if (mode != GEMM_MODE_AUTO && !(scaled && mode == GEMM_MODE_MX)) return bad;
+  if (tile != TILE_AUTO && !mxs_offers(tile)) return bad;
+  if (p.M < 0 || p.N < 0 || p.K <= 0 || p.lda < p.K || p.ldb < p.K) return bad;
+  if (in4 && (p.K % 256 || p.lda % 2 || p.ldb % 2)) return bad;
+  // whole 64-row gate / up groups; whole 32-column blocks, as many as the GEMM that reads them
+  // takes per K-tile row
+  if ((glu && p.N % 64) || (qout && cols % (q4 ? 256 : 128))) return bad;
+  // (a dense fp4 launch without groups or a gate takes grouped C rows, as it always has)
+  const bool plain_c_rows = !in4 || qout || glu || grouped || kgrouped;
+  if (plain_operands_only(p, plain_c_rows, true, bad) != hipSuccess) return bad;
+  if ((grouped || kgrouped) &&
+      (p.grp_offs == nullptr || p.ngroups <= 0 || p.ngroups > kMaxGroups))
+    return bad;
+  if (grouped) {
+    const int64_t esz2 = in4 ? 1 : 2 * dtype_size(din);  // twice the element size
+    if (p.b_gstride < 0 || p.b_gstride * esz2 % 32 ||
+        (p.ngroups > 1 && p.b_gstride < (int64_t)p.N * p.ldb))
+      return bad;
+    if (scaled && (p.b_scale_gstride < 0 || p.b_scale_gstride % sal ||
+                   (p.ngroups > 1 && p.b_scale_gstride < (int64_t)p.N * p.b_scale_ld)))
+      return bad;
+    if (grouped_grid_bound(p.M, p.ngroups, 128, (p.N + 127) / 128) > 0x7FFFFFFFLL) return bad;
   }
-  if (tile == TILE_AUTO) tile = mxs_tile_for(choose_tile(p.M, p.N, p.K, din));
-  if (tile < 0) return hipErrorInvalidValue;
-  GemmArgs g = p;
-  g.glu = 1;
-  if (grouped_launch(p)) return launch_grouped_checked(g, din, dout, tile, s);
-  if (qout) return q4 ? launch_qout_fp4(g, din, tile, s) : launch_qout_fp8(g, din, tile, s);
-  if (in4) return launch_fast_mx4(g, dout, tile, s);
-  if (scaled) return launch_fast_mxs(g, dout, tile, s);
-  return launch_fast(g, din, dout, tile, s);
-}
-
-// A grouped launch with bf16 / f16 operands or block-scaled fp8 ones and a dense output (the gated,
-// quantising and fp4 forms go through the functions above): the grouped tiled kernel or
-// hipErrorInvalidValue. Unit-scale fp8 has no grouped form.
-static hipError_t gemm_launch_grouped_dense(const GemmArgs& p, int din, int dout, int tile,
-                                            int mode, hipStream_t s) {
-  const bool scaled = din == DT_FP8;
-  if (din != DT_BF16 && din != DT_F16 && !scaled) return hipErrorInvalidValue;
-  if (scaled ? (p.a_scale == nullptr || p.b_scale == nullptr)
-             : (p.a_scale != nullptr || p.b_scale != nullptr))
-    return hipErrorInvalidValue;
-  if (dout != DT_F32 && !(scaled ? dout == DT_BF16 || dout == DT_F16 : dout == din))
-    return hipErrorInvalidValue;
-  if (mode < GEMM_MODE_AUTO || mode > GEMM_MODE_MX || (!scaled && mode == GEMM_MODE_MX))
-    return hipErrorInvalidValue;
-  if (p.K <= 0) return hipErrorInvalidValue;
+  if (kgrouped) {
+    const int MOD = in4 ? 256 : 128;
+    if (!scaled || qout || glu || p.act != ACT_NONE) return bad;
+    if (p.b_gstride != 0 || p.b_scale_gstride != 0 || p.kgrp_rows < 0 || p.K % MOD) return bad;
+    if (p.K < kgrouped_capacity(p.kgrp_rows, p.ngroups, MOD)) return bad;
+  }
   if (p.M == 0 || p.N == 0) return hipSuccess;
-  if (p.a == nullptr || p.b == nullptr || p.c == nullptr || p.lda < p.K || p.ldb < p.K ||
-      p.ldc < p.N || !gemm_fast_path_ok(p, din, dout))
-    return hipErrorInvalidValue;
-  if (scaled && !scale_operands_ok(p, 4)) return hipErrorInvalidValue;
+  const GemmArgs q = fp4_byte_view(p, in4, q4);
+  if (p.a == nullptr || p.b == nullptr || p.c == nullptr || p.ldc < cols || (q4 && p.ldc % 2) ||
+      !gemm_fast_path_ok(q, in4 ? DT_U8 : din, qout ? DT_U8 : dout))
+    return bad;
+  if (scaled && !scale_operands_ok(p, sal)) return bad;
+  if (qout && (q.ldc % 16 || ((uintptr_t)p.c & 15) || ((uintptr_t)p.c_scale & (cal - 1)) ||
+               p.c_scale_ld % cal || p.c_scale_ld < cols / 32 ||
+               (int64_t)p.M * p.c_scale_ld >= (int64_t(1) << 31)))
+    return bad;
+  if (kgrouped && (p.c_kgstride < 0 || p.c_kgstride * dtype_size(dout) % 8 ||
+                   (p.ngroups > 1 && p.c_kgstride < (int64_t)p.M * p.ldc)))
+    return bad;
   if (tile == TILE_AUTO) tile = mxs_tile_for(choose_tile(p.M, p.N, p.K, din));
-  if (tile < 0) return hipErrorInvalidValue;
-  return launch_grouped_checked(p, din, dout, tile, s);
-}
-
-// K-grouped launches (GemmArgs::kgrouped): the K-grouped tiled kernel or hipErrorInvalidValue. The
-// offsets are device memory and are never read here. What the M-grouped form refuses about flags,
-// tables, grouped rows, K-split, all-gather, tile codes and the number of groups is refused here
-// too, and so are an activation, a gate, a quantised output and unscaled operands. K is the
-// operands' column extent: whole K-tiles, at least the capacity of (T, E, MOD), so no content of
-// the offsets reaches a column outside an operand row (tile_map.h); rows and scales as the scaled
-// flavour it runs asks for them. The groups' outputs lie c_kgstride elements apart without
-// overlap, 8-byte aligned as c is.
-static hipError_t gemm_launch_kgrouped(const GemmArgs& p, int din, int dout, int tile, int mode,
-                                       hipStream_t s) {
-  const bool in4 = din == DT_FP4;
-  const int MOD = in4 ? 256 : 128;
-  if (p.grp_offs == nullptr || p.ngroups <= 0 || p.ngroups > kMaxGroups)
-    return hipErrorInvalidValue;
-  if (din != DT_FP8 && !in4) return hipErrorInvalidValue;
-  if (p.a_scale == nullptr || p.b_scale == nullptr) return hipErrorInvalidValue;
-  if (dout != DT_F32 && dout != DT_BF16 && dout != DT_F16) return hipErrorInvalidValue;
-  if (p.act != ACT_NONE || p.glu || p.c_scale != nullptr) return hipErrorInvalidValue;
-  if (mode != GEMM_MODE_AUTO && mode != GEMM_MODE_MX) return hipErrorInvalidValue;
-  if (tile != TILE_AUTO && !mxs_offers(tile)) return hipErrorInvalidValue;
-  if (p.b_gstride != 0 || p.b_scale_gstride != 0) return hipErrorInvalidValue;
-  if (p.M < 0 || p.N < 0 || p.K <= 0 || p.K % MOD || p.kgrp_rows < 0)
-    return hipErrorInvalidValue;
-  const hipError_t e = plain_operands_only(p, true, true, hipErrorInvalidValue);
-  if (e != hipSuccess) return e;
-  if (p.K < kgrouped_capacity(p.kgrp_rows, p.ngroups, MOD)) return hipErrorInvalidValue;
-  if (p.M == 0 || p.N == 0) return hipSuccess;
-  if (in4 && (p.lda % 2 || p.ldb % 2)) return hipErrorInvalidValue;
-  if (p.a == nullptr || p.b == nullptr || p.c == nullptr || p.lda < p.K || p.ldb < p.K ||
-      p.ldc < p.N || !gemm_fast_path_ok(fp4_byte_view(p, in4, false), in4 ? DT_U8 : din, dout))
-    return hipErrorInvalidValue;
-  if (!scale_operands_ok(p, in4 ? 8 : 4)) return hipErrorInvalidValue;
-  if (p.c_kgstride < 0 || p.c_kgstride * dtype_size(dout) % 8 ||
-      (p.ngroups > 1 && p.c_kgstride < (int64_t)p.M * p.ldc))
-    return hipErrorInvalidValue;
-  if (tile == TILE_AUTO) tile = mxs_tile_for(choose_tile(p.M, p.N, p.K, din));
-  if (tile < 0) return hipErrorInvalidValue;
-  const int64_t tiles = (int64_t)((p.M + tile_rows(tile) - 1) / tile_rows(tile)) *
-                        ((p.N + tile_cols(tile) - 1) / tile_cols(tile));
-  if (tiles * p.ngroups > 0x7FFFFFFFLL) return hipErrorInvalidValue;
-  if (launch_kgrouped == nullptr) return hipErrorNotSupported;
-  return launch_kgrouped(p, din, dout, tile, s);
+  if (tile < 0) return bad;
+  p.glu = glu;
+  if (kgrouped) {
+    const int64_t tiles = (int64_t)((p.M + tile_rows(tile) - 1) / tile_rows(tile)) *
+                          ((p.N + tile_cols(tile) - 1) / tile_cols(tile));
+    if (tiles * p.ngroups > 0x7FFFFFFFLL) return bad;
+    // (the grouped entries are weak: gemm_entry.h)
+    return launch_kgrouped == nullptr ? hipErrorNotSupported : launch_kgrouped(p, din, dout, tile, s);
+  }
+  if (grouped)
+    return launch_grouped == nullptr ? hipErrorNotSupported : launch_grouped(p, din, dout, tile, s);
+  if (qout) return q4 ? launch_qout_fp4(p, din, tile, s) : launch_qout_fp8(p, din, tile, s);
+  if (in4) return launch_fast_mx4(p, dout, tile, s);
+  if (scaled) return launch_fast_mxs(p, dout, tile, s);
+  return launch_fast(p, din, dout, tile, s);
 }
 
 hipError_t gemm_launch(const GemmArgs& p_in, int din, int dout, int tile, int mode,
@@ -342,18 +215,10 @@ hipError_t gemm_launch(const GemmArgs& p_in, int din, int dout, int tile, int mo
   if (p.c_grp <= 0) { p.c_grp = p.M > 0 ? p.M : 1; p.c_gstride = p.c_grp; }
   // known codes only (the retired families' codes are refused, not rerouted)
   if (tile != TILE_AUTO && tile_slot(tile) < 0) return hipErrorInvalidValue;
-  if (p.kgrouped) return gemm_launch_kgrouped(p, din, dout, tile, mode, s);
-  const bool grouped = grouped_launch(p);
-  if (grouped) {
-    const hipError_t e = grouped_operands_ok(p, din, tile, mode);
-    if (e != hipSuccess) return e;
-  }
-  if (p.glu) return gemm_launch_glu(p, din, dout, tile, mode, s);
-  // quantised output: dout fp8 / fp4 and output scales go together
-  if (dout == DT_FP8 || dout == DT_FP4) return gemm_launch_qout(p, din, dout, tile, mode, s);
-  if (p.c_scale != nullptr) return hipErrorInvalidValue;
-  if (din == DT_FP4) return gemm_launch_fp4(p, dout, tile, mode, s);
-  if (grouped) return gemm_launch_grouped_dense(p, din, dout, tile, mode, s);
+  // every form beyond the plain launch; a quantised output and its scales go together
+  if (p.kgrouped || grouped_launch(p) || p.glu || din == DT_FP4 || dout == DT_FP8 ||
+      dout == DT_FP4 || p.c_scale != nullptr)
+    return gemm_launch_form(p, din, dout, tile, mode, s);
   // MX block scales: both or neither; with them the tiled kernel's scaled flavour or a refusal,
   // never unit scales in their place
   if ((p.a_scale != nullptr) != (p.b_scale != nullptr)) return hipErrorInvalidValue;

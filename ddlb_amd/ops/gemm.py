@@ -72,14 +72,35 @@ def _check_placement(*ts):
         raise ValueError("operands must be row-major with unit inner stride")
 
 
+def _check_same_dtype(a, w):
+    if a.dtype != w.dtype:
+        raise TypeError(f"A dtype {a.dtype} != W dtype {w.dtype}")
+
+
+def _check_k(a, w):
+    """``a [.., K]`` against ``w [.., N, K]`` (a stack of experts is shown whole)."""
+    if a.shape[1] != w.shape[-1]:
+        raise ValueError(f"K mismatch: A {tuple(a.shape)} vs W {tuple(w.shape)}")
+
+
+def _check_32_bits(M, N, K):
+    if M >= 2 ** 31 or N >= 2 ** 31 or K >= 2 ** 31:
+        raise ValueError("dimensions must fit in 32 bits")
+
+
+def _stream(stream, a):
+    """The raw HIP stream of a launch: the caller's, or the current one of ``a``'s device."""
+    import torch
+
+    return stream if stream is not None else torch.cuda.current_stream(a.device).cuda_stream
+
+
 def _check_operands(a, w, out, M, a_rows_phys):
     import torch
 
     _check_placement(a, w, out)
-    if a.dtype != w.dtype:
-        raise TypeError(f"A dtype {a.dtype} != W dtype {w.dtype}")
-    if a.shape[1] != w.shape[1]:
-        raise ValueError(f"K mismatch: A {tuple(a.shape)} vs W {tuple(w.shape)}")
+    _check_same_dtype(a, w)
+    _check_k(a, w)
     if out.shape[1] < w.shape[0]:
         raise ValueError(f"output has {out.shape[1]} columns < N={w.shape[0]}")
     if a_rows_phys > a.shape[0]:
@@ -160,6 +181,11 @@ _MX_FP8 = _ScaledFormat(1, 128, 4, SCALED_TILES, "block scales", True, "block sc
 _MX_FP4 = _ScaledFormat(2, 256, 8, SCALED_FP4_TILES, "the fp4 GEMM", False, "fp4 operands", "")
 
 
+def _check_tile(noun, tile, note="", be="is", tiles=SCALED_TILES):
+    if tile != "auto" and tile not in tiles:
+        raise ValueError(f"{noun} {be} offered for tile auto / {tiles}, not {tile!r}{note}")
+
+
 def _check_block_scaled(f, a, w, a_scale, w_scale, M, tile, mode, a_grp, ksplit):
     """The refusals the block-scaled formats share, before anything is launched."""
     import torch
@@ -167,9 +193,7 @@ def _check_block_scaled(f, a, w, a_scale, w_scale, M, tile, mode, a_grp, ksplit)
     be, need, do = (("are", "need", "do") if f.plural else ("is", "needs", "does"))
     if mode not in ("auto", "mx"):
         raise ValueError(f"{f.runs} run the MX kernel (mode auto / mx), not mode={mode!r}")
-    if tile != "auto" and tile not in f.tiles:
-        raise ValueError(f"{f.noun} {be} offered for tile auto / {f.tiles}, not "
-                         f"{tile!r}{f.tile_note}")
+    _check_tile(f.noun, tile, f.tile_note, be, f.tiles)
     if a_grp not in (0, M):
         raise ValueError(f"{f.noun} {need} plain A rows (no grouped A rows)")
     if ksplit > 1:
@@ -229,73 +253,168 @@ def out_quant_dtype(out_quant: str):
     return _fp4_dtype() if out_quant == "mxfp4" else torch.float8_e4m3fn
 
 
-def _check_out_quant(a, w, out_quant, out=None, out_scale=None, *, a_scale=None, w_scale=None,
-                     tile: str = "auto", mode: str = "auto", M: Optional[int] = None,
-                     a_grp: int = 0, c_grp: int = 0, ksplit: int = 0, out_dtype=None):
-    """Every refusal of the quantised-output GEMM (``out_quant="mx" | "mxfp4"``), on the host and
-    before anything is loaded or launched (CPU tensors pass through it). ``out`` / ``out_scale``
-    are checked when given. Returns ``(M, N, K)`` in elements."""
+class _Form(NamedTuple):
+    """What the launch forms of the tiled kernel differ in on the host: the wording of their
+    refusals."""
+    noun: str       # the subject of the messages
+    tile_note: str
+    takes: str      # the subject of the operand refusal
+    no_scales: str  # fp8 (fp4) operands without their scales
+    fast_path: str  # what the MFMA fast path asks of the form
+
+
+_WHOLE_K_TILES = ("16-byte-aligned operand rows, 8-byte-aligned output rows and K a whole number "
+                  "of 128-byte K-tiles")
+_QOUT = _Form("a quantised output", "", "out_quant",
+              "a quantised output from fp8 operands needs a_scale and w_scale (there is no "
+              "unit-scale kernel with this epilogue)",
+              "16-byte-aligned operand rows and K a whole number of 128-byte K-tiles")
+_GLU = _Form("a gated epilogue", " (the ping-pong, interleaved and 256x256 kernels have none)",
+             "glu", "a gated epilogue on fp8 operands needs a_scale and w_scale (the unit-scale "
+             "kernels have none)", _WHOLE_K_TILES)
+_GROUPED = _Form("a grouped GEMM",
+                 " (the ping-pong, interleaved and 256x256 kernels have no grouped form)",
+                 "a grouped GEMM", "a grouped GEMM on fp8 / fp4 operands needs a_scale and "
+                 "w_scale (the unit-scale kernels have no grouped form)", _WHOLE_K_TILES)
+_KGROUPED = _Form("a K-grouped GEMM", "", "a K-grouped GEMM",
+                  "a K-grouped GEMM needs a_scale and w_scale (the unit-scale kernels have no "
+                  "K-grouped form)", "16-byte-aligned operand rows, 8-byte-aligned output rows")
+
+
+class _Tiled(NamedTuple):
+    """What :func:`_check_tiled` found: the extents in elements and the output dtype."""
+    M: int
+    N: int
+    K: int
+    odt: object
+
+
+def _known_out_quant(out_quant, optional: bool):
+    if out_quant not in OUT_QUANTS and not (optional and out_quant is None):
+        raise ValueError(f"out_quant must be None or one of {OUT_QUANTS}, not {out_quant!r}")
+    if out_quant == "mxfp4" and _fp4_dtype() is None:
+        raise TypeError("out_quant='mxfp4' needs torch.float4_e2m1fn_x2")
+
+
+def _check_quant_dtype(out_quant, out_dtype):
+    qdt = out_quant_dtype(out_quant)
+    if out_dtype is not None and out_dtype != qdt:
+        raise TypeError(f"out_quant={out_quant!r} writes {qdt}, not out_dtype={out_dtype}")
+
+
+def _refuse_operands(f, a):
+    raise TypeError(f"{f.takes} takes bf16, f16, scaled fp8 or scaled fp4 operands, not {a.dtype}")
+
+
+def _check_dense_out(what, a, out, out_dtype, dense, rows, cols, groups=0):
+    """The dense output of a form (``what`` names it): its dtype, ``dense[0]`` unless ``out`` or
+    ``out_dtype`` says otherwise, among the ones the operands pair with; ``out``, where given, on
+    the operands' device as ``[>= rows, cols]`` rows, or exactly ``[groups, rows, cols]``."""
+    odt = out.dtype if out is not None else (out_dtype or dense[0])
+    if out is not None and out_dtype is not None and out_dtype != out.dtype:
+        raise TypeError(f"out is {out.dtype}, out_dtype={out_dtype}")
+    if odt not in dense:
+        raise TypeError(f"{what} writes one of {dense}, not {odt}")
+    if out is None:
+        return odt
+    if out.device != a.device:
+        raise ValueError(f"out is on {out.device}, the operands on {a.device}")
+    if groups:
+        if out.dim() != 3 or tuple(out.shape) != (groups, rows, cols):
+            raise ValueError(f"out must have shape {(groups, rows, cols)}, not {tuple(out.shape)}")
+        need = ", rows of at least N and groups at least M rows apart"
+        laid = out.stride(1) >= cols and (groups == 1 or out.stride(0) >= rows * out.stride(1))
+    else:
+        if out.dim() != 2 or out.shape[0] < rows or out.shape[1] != cols:
+            raise ValueError(f"out must have shape (>= {rows}, {cols}), not {tuple(out.shape)}")
+        need = f" and a row stride of at least {cols}"
+        laid = out.stride(0) >= cols
+    if out.stride(-1) != 1 or not laid:
+        raise ValueError(f"out needs unit inner stride{need} (strides {tuple(out.stride())})")
+    if groups and out.stride(0) * out.element_size() % 8:
+        raise ValueError("the groups' outputs must be a multiple of 8 bytes apart")
+    return odt
+
+
+def _check_tiled(f, a, w, out, out_scale, *, out_quant, out_dtype, a_scale, w_scale, tile, mode,
+                 M, a_grp, c_grp, ksplit, glu=False, own=None):
+    """The rules the forms of the tiled kernel share, on the host and before anything is loaded
+    or launched, worded for the form ``f``: ranks, K, ``M``; the entry point's ``own(N)`` rules;
+    mode, tile, K-split, plain rows; the operand kind, the scales it carries and the dense dtypes
+    it pairs with; the 32-bit extents; the output, dense or (``out_quant``) quantised, of ``N``
+    columns or (``glu``) ``N / 2``. ``out`` / ``out_scale`` are checked when given."""
     import torch
     from types import SimpleNamespace
 
-    if out_quant not in OUT_QUANTS:
-        raise ValueError(f"out_quant must be None or one of {OUT_QUANTS}, not {out_quant!r}")
-    q4 = out_quant == "mxfp4"
-    if q4 and _fp4_dtype() is None:
-        raise TypeError("out_quant='mxfp4' needs torch.float4_e2m1fn_x2")
-    qdt = out_quant_dtype(out_quant)
     if a.dim() != 2 or w.dim() != 2:
         raise ValueError("native GEMM expects 2-D operands")
     fp4 = _is_fp4(a) or _is_fp4(w)
     M = a.shape[0] if M is None else int(M)
     N = w.shape[0]
     K = 2 * a.shape[1] if fp4 else a.shape[1]
-    if a.shape[1] != w.shape[1]:
-        raise ValueError(f"K mismatch: A {tuple(a.shape)} vs W {tuple(w.shape)}")
+    _check_k(a, w)
     if not 0 <= M <= a.shape[0]:
         raise ValueError(f"M = {M} is outside A's {a.shape[0]} rows")
-    if out_dtype is not None and out_dtype != qdt:
-        raise TypeError(f"out_quant={out_quant!r} writes {qdt}, not out_dtype={out_dtype}")
-    nmod = 256 if q4 else 128
-    if N % nmod:
-        raise ValueError(f"out_quant={out_quant!r} needs N % {nmod} == 0 (N = {N}): whole "
-                         "32-column blocks, as many as the GEMM that reads them takes per K-tile")
+    if own is not None:
+        own(N)
     if mode == "generic":
-        raise ValueError("a quantised output comes from the tiled MFMA kernel, not mode='generic'")
+        raise ValueError(f"{f.noun} comes from the tiled MFMA kernel, not mode='generic'")
     if mode not in MODES:
         raise ValueError(f"unknown mode {mode!r}")
-    if tile != "auto" and tile not in SCALED_TILES:
-        raise ValueError(f"a quantised output is offered for tile auto / {SCALED_TILES}, not "
-                         f"{tile!r}")
+    _check_tile(f.noun, tile, f.tile_note)
     if int(ksplit) > 1:
-        raise ValueError("a quantised output does not combine with a K-split")
+        raise ValueError(f"{f.noun} does not combine with a K-split")
     if a_grp not in (0, M) or c_grp not in (0, M):
-        raise ValueError("a quantised output needs plain A and C rows (no grouped rows)")
-    # the inputs: bf16, f16, block-scaled fp8, block-scaled fp4
+        raise ValueError(f"{f.noun} needs plain A and C rows (no grouped rows)")
+    # the inputs: bf16, f16, block-scaled fp8, block-scaled fp4; the dense outputs they pair with
+    dense = (torch.bfloat16, torch.float16, torch.float32)
     if fp4:
         _check_fp4(a, w, SimpleNamespace(dtype=torch.bfloat16), a_scale, w_scale, M, tile, mode,
                    a_grp, int(ksplit))
     elif a.dtype == torch.float8_e4m3fn or w.dtype == torch.float8_e4m3fn:
-        if a.dtype != w.dtype:
-            raise TypeError(f"A dtype {a.dtype} != W dtype {w.dtype}")
+        _check_same_dtype(a, w)
         if a_scale is None or w_scale is None:
-            raise ValueError("a quantised output from fp8 operands needs a_scale and w_scale "
-                             "(there is no unit-scale kernel with this epilogue)")
+            raise ValueError(f.no_scales)
         _check_scales(a, w, a_scale, w_scale, M, tile, mode, a_grp, int(ksplit))
     elif a.dtype in (torch.bfloat16, torch.float16):
-        if a.dtype != w.dtype:
-            raise TypeError(f"A dtype {a.dtype} != W dtype {w.dtype}")
+        _check_same_dtype(a, w)
         if a_scale is not None or w_scale is not None:
             raise TypeError(f"block scales need fp8 / fp4 operands, not {a.dtype}")
         if mode == "mx":
             raise ValueError(f"mode='mx' needs fp8 / fp4 operands, not {a.dtype}")
+        dense = (a.dtype, torch.float32)
     else:
-        raise TypeError(f"out_quant takes bf16, f16, scaled fp8 or scaled fp4 operands, not "
-                        f"{a.dtype}")
-    if M >= 2 ** 31 or N >= 2 ** 31 or K >= 2 ** 31:
-        raise ValueError("dimensions must fit in 32 bits")
-    _check_quant_outputs(a, out, out_scale, out_quant, M, N)
-    return M, N, K
+        _refuse_operands(f, a)
+    _check_32_bits(M, N, K)
+    cols = N // 2 if glu else N
+    if out_quant is None:
+        return _Tiled(M, N, K, _check_dense_out(f"{f.noun} on {a.dtype} operands", a, out,
+                                                out_dtype, dense, M, cols))
+    _check_quant_dtype(out_quant, out_dtype)
+    _check_quant_outputs(a, out, out_scale, out_quant, M, cols)
+    return _Tiled(M, N, K, out_quant_dtype(out_quant))
+
+
+def _check_out_quant(a, w, out_quant, out=None, out_scale=None, *, a_scale=None, w_scale=None,
+                     tile: str = "auto", mode: str = "auto", M: Optional[int] = None,
+                     a_grp: int = 0, c_grp: int = 0, ksplit: int = 0, out_dtype=None):
+    """Every refusal of the quantised-output GEMM (``out_quant="mx" | "mxfp4"``), on the host and
+    before anything is loaded or launched (CPU tensors pass through it). ``out`` / ``out_scale``
+    are checked when given. Returns ``(M, N, K)`` in elements."""
+    _known_out_quant(out_quant, optional=False)
+
+    def own(N):
+        _check_quant_dtype(out_quant, out_dtype)
+        nmod = 256 if out_quant == "mxfp4" else 128
+        if N % nmod:
+            raise ValueError(f"out_quant={out_quant!r} needs N % {nmod} == 0 (N = {N}): whole "
+                             "32-column blocks, as many as the GEMM that reads them takes per "
+                             "K-tile")
+
+    return tuple(_check_tiled(_QOUT, a, w, out, out_scale, out_quant=out_quant,
+                              out_dtype=out_dtype, a_scale=a_scale, w_scale=w_scale, tile=tile,
+                              mode=mode, M=M, a_grp=a_grp, c_grp=c_grp, ksplit=ksplit,
+                              own=own)[:3])
 
 
 def _check_quant_outputs(a, out, out_scale, out_quant, M, cols):
@@ -349,43 +468,46 @@ def _launch(C, a, w, c, M, N, K, tile, mode, s, *, a_grp=0, a_gstride=0, c_grp=0
     C.gemm(*args)
 
 
-def _gemm_out_quant(a, w, out, out_scale, out_quant, *, out_dtype, tile, mode, M, a_grp, c_grp,
-                    stream, act, ksplit, a_scale, w_scale):
-    """The quantised-output launch: ``(q, s)`` written by the tiled kernel's epilogue. Every
-    refusal comes first, before the extension is loaded."""
+def _need_fast_path(C, message, a, w, out, M, N, K, dout):
+    """The MFMA fast path's alignment on the operands as the byte / element matrices the kernel
+    reads (``K`` in elements; ``w`` and ``out`` 2-D: one expert's weight, one group's output)."""
+    fp4 = _is_fp4(a)
+    if M and N and not C.gemm_fast_path_ok(a.data_ptr(), w.data_ptr(), out.data_ptr(),
+                                           a.stride(0), w.stride(0), out.stride(0), M, N,
+                                           K // 2 if fp4 else K,
+                                           DT_U8 if fp4 else dtype_code(a.dtype), dout):
+        raise ValueError(message)
+
+
+def _run_tiled(f, t, a, w, out, out_scale, launch, *, out_quant=None, glu=False, groups=0,
+               stream=None):
+    """The launch tail the forms share, after every refusal of ``_check_*`` (``t``): load the
+    extension, allocate ``out`` / ``out_scale`` where absent (never zero-filled), placement, the
+    fast path, the stream, ``launch(C, out, out_scale, s)``, and what ``gemm`` returns. ``w`` may
+    be a stack of experts and ``out`` one of ``groups`` matrices."""
     import torch
 
-    if act not in ACTS:
-        raise ValueError(f"unknown activation {act!r}")
-    M, N, K = _check_out_quant(a, w, out_quant, out, out_scale, a_scale=a_scale, w_scale=w_scale,
-                               tile=tile, mode=mode, M=M, a_grp=a_grp, c_grp=c_grp, ksplit=ksplit,
-                               out_dtype=out_dtype)
     C = load()
-    q4 = out_quant == "mxfp4"
-    fp4 = _is_fp4(a)
-    ncol = N // 2 if q4 else N
-    _check_placement(a, w)
-    # dense rows are what the consumer asks of a / a_scale: N % 128 (256) makes a data row a
-    # multiple of 16 bytes and a scale row a multiple of 4 (8)
-    if out is None:
-        out = torch.empty((M, ncol), dtype=torch.uint8,
-                          device=a.device).view(out_quant_dtype(out_quant))
-    if out_scale is None:
-        out_scale = torch.empty((M, N // 32), dtype=torch.uint8, device=a.device)
-    kb = K // 2 if fp4 else K  # the operands as the byte / element matrices the kernel reads
-    if M and N and not C.gemm_fast_path_ok(a.data_ptr(), w.data_ptr(), out.data_ptr(),
-                                           a.stride(0), w.stride(0), out.stride(0), M, N, kb,
-                                           DT_U8 if fp4 else dtype_code(a.dtype), DT_U8):
-        raise ValueError("a quantised output needs the MFMA fast path: 16-byte-aligned operand "
-                         "rows and K a whole number of 128-byte K-tiles")
-    s = stream if stream is not None else torch.cuda.current_stream(a.device).cuda_stream
-    # (ksplit 1: neither a requested nor the automatic K-split engages on this path)
-    _launch(C, a, w, out, M, N, K, tile, mode, s, act=ACTS[act], a_scale=a_scale,
-            w_scale=w_scale, out_scale=out_scale)
+    M, N, K, odt = t
+    cols = N // 2 if glu else N
+    if out is None and out_quant is not None:
+        out = torch.empty((M, cols // 2 if out_quant == "mxfp4" else cols), dtype=torch.uint8,
+                          device=a.device).view(odt)
+    elif out is None:
+        out = torch.empty((groups, M, cols) if groups else (M, cols), dtype=odt, device=a.device)
+    if out_quant is not None and out_scale is None:
+        out_scale = torch.empty((M, cols // 32), dtype=torch.uint8, device=a.device)
+    w2, out2 = (w[0] if w.dim() == 3 else w), (out[0] if groups else out)
+    _check_placement(a, w2, out2)
+    _need_fast_path(C, f"{f.noun} needs the MFMA fast path: {f.fast_path}", a, w2, out2, M, N, K,
+                    DT_U8 if out_quant else dtype_code(odt))
+    s = _stream(stream, a)
+    launch(C, out, out_scale, s)
     if stream is not None:  # the outputs stay allocated until that stream reaches them
         out.record_stream(torch.cuda.ExternalStream(s))
-        out_scale.record_stream(torch.cuda.ExternalStream(s))
-    return out[:M], out_scale[:M]
+        if out_scale is not None:
+            out_scale.record_stream(torch.cuda.ExternalStream(s))
+    return out if out_quant is None else (out[:M], out_scale[:M])
 
 
 GLU_GROUP = 32  # gate / up rows alternate in groups of one MX block (GemmArgs::glu)
@@ -449,126 +571,24 @@ def _check_glu(a, w, out=None, out_scale=None, *, out_quant=None, out_dtype=None
     or launched (CPU tensors pass through it). ``out`` / ``out_scale`` are checked when given.
     Returns ``(M, N, K, output dtype)``: ``N`` the rows of ``w``; the output has ``N / 2``
     columns."""
-    import torch
-    from types import SimpleNamespace
-
     if act not in ACTS:
         raise ValueError(f"unknown activation {act!r}")
-    if out_quant is not None and out_quant not in OUT_QUANTS:
-        raise ValueError(f"out_quant must be None or one of {OUT_QUANTS}, not {out_quant!r}")
-    q4 = out_quant == "mxfp4"
-    if q4 and _fp4_dtype() is None:
-        raise TypeError("out_quant='mxfp4' needs torch.float4_e2m1fn_x2")
+    _known_out_quant(out_quant, optional=True)
     if out_quant is None and out_scale is not None:
         raise ValueError("out_scale goes with out_quant")
-    if a.dim() != 2 or w.dim() != 2:
-        raise ValueError("native GEMM expects 2-D operands")
-    fp4 = _is_fp4(a) or _is_fp4(w)
-    M = a.shape[0] if M is None else int(M)
-    N = w.shape[0]
-    K = 2 * a.shape[1] if fp4 else a.shape[1]
-    if a.shape[1] != w.shape[1]:
-        raise ValueError(f"K mismatch: A {tuple(a.shape)} vs W {tuple(w.shape)}")
-    if not 0 <= M <= a.shape[0]:
-        raise ValueError(f"M = {M} is outside A's {a.shape[0]} rows")
-    nmod = 512 if q4 else 256 if out_quant else 2 * GLU_GROUP
-    if N % nmod:
-        why = ("N / 2 in whole 32-column blocks, as many as the GEMM that reads them takes per "
-               "K-tile" if out_quant else "whole groups of 32 gate and 32 up rows")
-        raise ValueError(f"glu with out_quant={out_quant!r} needs N % {nmod} == 0 (N = {N}): {why}")
-    if mode == "generic":
-        raise ValueError("a gated epilogue comes from the tiled MFMA kernel, not mode='generic'")
-    if mode not in MODES:
-        raise ValueError(f"unknown mode {mode!r}")
-    if tile != "auto" and tile not in SCALED_TILES:
-        raise ValueError(f"a gated epilogue is offered for tile auto / {SCALED_TILES}, not "
-                         f"{tile!r} (the ping-pong, interleaved and 256x256 kernels have none)")
-    if int(ksplit) > 1:
-        raise ValueError("a gated epilogue does not combine with a K-split")
-    if a_grp not in (0, M) or c_grp not in (0, M):
-        raise ValueError("a gated epilogue needs plain A and C rows (no grouped rows)")
-    # the inputs: bf16, f16, block-scaled fp8, block-scaled fp4; the dense outputs they pair with
-    if fp4:
-        _check_fp4(a, w, SimpleNamespace(dtype=torch.bfloat16), a_scale, w_scale, M, tile, mode,
-                   a_grp, int(ksplit))
-        dense = (torch.bfloat16, torch.float16, torch.float32)
-    elif a.dtype == torch.float8_e4m3fn or w.dtype == torch.float8_e4m3fn:
-        if a.dtype != w.dtype:
-            raise TypeError(f"A dtype {a.dtype} != W dtype {w.dtype}")
-        if a_scale is None or w_scale is None:
-            raise ValueError("a gated epilogue on fp8 operands needs a_scale and w_scale "
-                             "(the unit-scale kernels have none)")
-        _check_scales(a, w, a_scale, w_scale, M, tile, mode, a_grp, int(ksplit))
-        dense = (torch.bfloat16, torch.float16, torch.float32)
-    elif a.dtype in (torch.bfloat16, torch.float16):
-        if a.dtype != w.dtype:
-            raise TypeError(f"A dtype {a.dtype} != W dtype {w.dtype}")
-        if a_scale is not None or w_scale is not None:
-            raise TypeError(f"block scales need fp8 / fp4 operands, not {a.dtype}")
-        if mode == "mx":
-            raise ValueError(f"mode='mx' needs fp8 / fp4 operands, not {a.dtype}")
-        dense = (a.dtype, torch.float32)
-    else:
-        raise TypeError(f"glu takes bf16, f16, scaled fp8 or scaled fp4 operands, not {a.dtype}")
-    if M >= 2 ** 31 or N >= 2 ** 31 or K >= 2 ** 31:
-        raise ValueError("dimensions must fit in 32 bits")
-    if out_quant is not None:
-        qdt = out_quant_dtype(out_quant)
-        if out_dtype is not None and out_dtype != qdt:
-            raise TypeError(f"out_quant={out_quant!r} writes {qdt}, not out_dtype={out_dtype}")
-        _check_quant_outputs(a, out, out_scale, out_quant, M, N // 2)
-        return M, N, K, qdt
-    odt = out.dtype if out is not None else (out_dtype or dense[0])
-    if out is not None and out_dtype is not None and out_dtype != out.dtype:
-        raise TypeError(f"out is {out.dtype}, out_dtype={out_dtype}")
-    if odt not in dense:
-        raise TypeError(f"a gated epilogue on {a.dtype} operands writes one of {dense}, not {odt}")
-    if out is not None:
-        if out.device != a.device:
-            raise ValueError(f"out is on {out.device}, the operands on {a.device}")
-        if out.dim() != 2 or out.shape[0] < M or out.shape[1] != N // 2:
-            raise ValueError(f"out must have shape (>= {M}, {N // 2}), not {tuple(out.shape)}")
-        if out.stride(1) != 1 or out.stride(0) < N // 2:
-            raise ValueError(f"out needs unit inner stride and a row stride of at least "
-                             f"{N // 2} (strides {tuple(out.stride())})")
-    return M, N, K, odt
 
+    def own(N):
+        nmod = 512 if out_quant == "mxfp4" else 256 if out_quant else 2 * GLU_GROUP
+        if N % nmod:
+            why = ("N / 2 in whole 32-column blocks, as many as the GEMM that reads them takes "
+                   "per K-tile" if out_quant else "whole groups of 32 gate and 32 up rows")
+            raise ValueError(f"glu with out_quant={out_quant!r} needs N % {nmod} == 0 "
+                             f"(N = {N}): {why}")
 
-def _gemm_glu(a, w, out, out_scale, *, out_quant, out_dtype, tile, mode, M, a_grp, c_grp, stream,
-              act, ksplit, a_scale, w_scale):
-    """The gated launch: ``act(gate) * up`` out of the tiled kernel's epilogue, ``[M, N / 2]``
-    dense or as ``(q, s)``. Every refusal comes first, before the extension is loaded."""
-    import torch
-
-    M, N, K, odt = _check_glu(a, w, out, out_scale, out_quant=out_quant, out_dtype=out_dtype,
-                              a_scale=a_scale, w_scale=w_scale, tile=tile, mode=mode, M=M,
-                              a_grp=a_grp, c_grp=c_grp, ksplit=ksplit, act=act)
-    C = load()
-    fp4, q4 = _is_fp4(a), out_quant == "mxfp4"
-    _check_placement(a, w)
-    if out is None and out_quant is not None:
-        out = torch.empty((M, N // 4 if q4 else N // 2), dtype=torch.uint8,
-                          device=a.device).view(odt)
-    elif out is None:
-        out = torch.empty((M, N // 2), dtype=odt, device=a.device)
-    if out_quant is not None and out_scale is None:
-        out_scale = torch.empty((M, N // 64), dtype=torch.uint8, device=a.device)
-    kb = K // 2 if fp4 else K  # the operands as the byte / element matrices the kernel reads
-    if M and N and not C.gemm_fast_path_ok(a.data_ptr(), w.data_ptr(), out.data_ptr(),
-                                           a.stride(0), w.stride(0), out.stride(0), M, N, kb,
-                                           DT_U8 if fp4 else dtype_code(a.dtype),
-                                           DT_U8 if out_quant else dtype_code(odt)):
-        raise ValueError("a gated epilogue needs the MFMA fast path: 16-byte-aligned operand "
-                         "rows, 8-byte-aligned output rows and K a whole number of 128-byte "
-                         "K-tiles")
-    s = stream if stream is not None else torch.cuda.current_stream(a.device).cuda_stream
-    _launch(C, a, w, out, M, N, K, tile, mode, s, act=ACTS[act], a_scale=a_scale,
-            w_scale=w_scale, out_scale=out_scale, glu=True)
-    if stream is not None:  # the outputs stay allocated until that stream reaches them
-        out.record_stream(torch.cuda.ExternalStream(s))
-        if out_scale is not None:
-            out_scale.record_stream(torch.cuda.ExternalStream(s))
-    return out if out_quant is None else (out[:M], out_scale[:M])
+    return tuple(_check_tiled(_GLU, a, w, out, out_scale, out_quant=out_quant,
+                              out_dtype=out_dtype, a_scale=a_scale, w_scale=w_scale, tile=tile,
+                              mode=mode, M=M, a_grp=a_grp, c_grp=c_grp, ksplit=ksplit, glu=True,
+                              own=own))
 
 
 def gemm(a, w, out=None, *, out_dtype=None, tile: str = "auto", mode: str = "auto",
@@ -612,17 +632,26 @@ def gemm(a, w, out=None, *, out_dtype=None, tile: str = "auto", mode: str = "aut
     refusal."""
     import torch
 
-    if glu:
-        return _gemm_glu(a, w, out, out_scale, out_quant=out_quant, out_dtype=out_dtype,
-                         tile=tile, mode=mode, M=M, a_grp=a_grp, c_grp=c_grp, stream=stream,
-                         act=act, ksplit=ksplit, a_scale=a_scale, w_scale=w_scale)
-    if out_quant is None and out_scale is not None:
+    if glu or out_quant is not None:
+        # every refusal first, before the extension is loaded; then one launch (neither a
+        # requested nor the automatic K-split engages on this path)
+        kw = dict(a_scale=a_scale, w_scale=w_scale, tile=tile, mode=mode, M=M, a_grp=a_grp,
+                  c_grp=c_grp, ksplit=ksplit, out_dtype=out_dtype)
+        if glu:
+            t = _Tiled(*_check_glu(a, w, out, out_scale, out_quant=out_quant, act=act, **kw))
+        elif act not in ACTS:
+            raise ValueError(f"unknown activation {act!r}")
+        else:
+            t = _Tiled(*_check_out_quant(a, w, out_quant, out, out_scale, **kw),
+                       out_quant_dtype(out_quant))
+        return _run_tiled(
+            _GLU if glu else _QOUT, t, a, w, out, out_scale,
+            lambda C, out, out_scale, s: _launch(C, a, w, out, t.M, t.N, t.K, tile, mode, s,
+                                                 act=ACTS[act], a_scale=a_scale, w_scale=w_scale,
+                                                 out_scale=out_scale, glu=glu),
+            out_quant=out_quant, glu=glu, stream=stream)
+    if out_scale is not None:
         raise ValueError("out_scale goes with out_quant")
-    if out_quant is not None:
-        return _gemm_out_quant(a, w, out, out_scale, out_quant, out_dtype=out_dtype,
-                               tile=tile, mode=mode, M=M, a_grp=a_grp, c_grp=c_grp,
-                               stream=stream, act=act, ksplit=ksplit, a_scale=a_scale,
-                               w_scale=w_scale)
     C = load()
     scaled = a_scale is not None or w_scale is not None
     fp4 = _is_fp4(a) or _is_fp4(w)
@@ -641,30 +670,21 @@ def gemm(a, w, out=None, *, out_dtype=None, tile: str = "auto", mode: str = "aut
         raise ValueError("a_gstride must be >= a_grp")
     if c_grp and (c_grp < 0 or c_gstride < c_grp):
         raise ValueError("c_gstride must be >= c_grp")
-    if M >= 2 ** 31 or N >= 2 ** 31 or K >= 2 ** 31:
-        raise ValueError("dimensions must fit in 32 bits")
-    s = stream if stream is not None else torch.cuda.current_stream(a.device).cuda_stream
+    _check_32_bits(M, N, K)
+    s = _stream(stream, a)
     plain = (a_grp in (0, M) and c_grp in (0, M) and ACTS[act] == 0 and out.stride(0) == N
              and mode != "generic" and a.dtype != torch.float64)
     S = int(ksplit)
-    if fp4:
-        _check_fp4(a, w, out, a_scale, w_scale, M, tile, mode, a_grp, S)
-        K = 2 * K  # elements; the leading dimensions go in elements too
-        if M and N and not C.gemm_fast_path_ok(a.data_ptr(), w.data_ptr(), out.data_ptr(),
-                                               a.stride(0), w.stride(0), out.stride(0), M, N,
-                                               K // 2, DT_U8, dtype_code(out.dtype)):
-            raise ValueError("the fp4 GEMM needs the MFMA fast path: 16-byte-aligned operand "
-                             "rows, 8-byte-aligned output rows")
-        _launch(C, a, w, out, M, N, K, tile, mode, s, c_grp=c_grp, c_gstride=c_gstride,
-                act=ACTS[act], a_scale=a_scale, w_scale=w_scale)
-        return out
-    if scaled:
-        _check_scales(a, w, a_scale, w_scale, M, tile, mode, a_grp, S)
-        if M and N and not C.gemm_fast_path_ok(a.data_ptr(), w.data_ptr(), out.data_ptr(),
-                                               a.stride(0), w.stride(0), out.stride(0), M, N, K,
-                                               DT_FP8, dtype_code(out.dtype)):
-            raise ValueError("block scales need the MFMA fast path: 16-byte-aligned operand "
-                             "rows, 8-byte-aligned output rows")
+    if fp4 or scaled:
+        f = _MX_FP4 if fp4 else _MX_FP8
+        if fp4:
+            _check_fp4(a, w, out, a_scale, w_scale, M, tile, mode, a_grp, S)
+        else:
+            _check_scales(a, w, a_scale, w_scale, M, tile, mode, a_grp, S)
+        K *= f.per_byte  # elements; the leading dimensions go in elements too
+        _need_fast_path(C, f"{f.noun} {'need' if f.plural else 'needs'} the MFMA fast path: "
+                        "16-byte-aligned operand rows, 8-byte-aligned output rows", a, w, out, M,
+                        N, K, dtype_code(out.dtype))
         _launch(C, a, w, out, M, N, K, tile, mode, s, c_grp=c_grp, c_gstride=c_gstride,
                 act=ACTS[act], a_scale=a_scale, w_scale=w_scale)
         return out
@@ -757,14 +777,30 @@ def grouped_reference(a, w, offsets):
     return out
 
 
+def _check_group_count(f, E):
+    if E < 1:
+        raise ValueError(f"{f.noun} needs at least one group")
+    if E > MAX_GROUPS:
+        raise ValueError(f"{f.noun} takes at most {MAX_GROUPS} groups, not {E}")
+
+
+def _check_offsets_dtype(offsets):
+    import torch
+
+    if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int32:
+        raise TypeError(f"offsets must be an int32 tensor, not "
+                        f"{getattr(offsets, 'dtype', type(offsets))}")
+
+
 def _check_grouped(a, w, offsets, out=None, out_scale=None, *, out_dtype=None,
                    tile: str = "auto", act: str = "none", a_scale=None, w_scale=None,
                    out_quant: Optional[str] = None, glu: bool = False):
     """Every refusal of the grouped GEMM, on the host and before anything is loaded or launched
     (CPU tensors pass through it; the offsets' content is never read). What the ungrouped forms
-    already refuse is refused by their own checks (:func:`_check_block_scaled`,
-    :func:`_check_out_quant`, :func:`_check_glu`), applied to ``a`` and an expert's slice of ``w``
-    and ``w_scale``. Returns ``(T, N, K, E, output dtype)``: ``N`` the rows of an expert's weight."""
+    already refuse is refused by their own checks (:func:`_check_tiled`, through
+    :func:`_check_out_quant` and :func:`_check_glu` for those forms), applied to ``a`` and an
+    expert's slice of ``w`` and ``w_scale``. Returns ``(T, N, K, E, output dtype)``: ``N`` the
+    rows of an expert's weight."""
     import torch
 
     if act not in ACTS:
@@ -776,13 +812,8 @@ def _check_grouped(a, w, offsets, out=None, out_scale=None, *, out_dtype=None,
         raise ValueError(f"a grouped GEMM takes a as [T, K] (2-D), not {tuple(a.shape)}")
     E, N = w.shape[0], w.shape[1]
     T = a.shape[0]
-    if E < 1:
-        raise ValueError("a grouped GEMM needs at least one group")
-    if E > MAX_GROUPS:
-        raise ValueError(f"a grouped GEMM takes at most {MAX_GROUPS} groups, not {E}")
-    if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int32:
-        raise TypeError(f"offsets must be an int32 tensor, not "
-                        f"{getattr(offsets, 'dtype', type(offsets))}")
+    _check_group_count(_GROUPED, E)
+    _check_offsets_dtype(offsets)
     if offsets.dim() != 1 or offsets.shape[0] != E + 1 or not offsets.is_contiguous():
         raise ValueError(f"offsets must be contiguous with shape ({E + 1},) for {E} groups, not "
                          f"{tuple(offsets.shape)}")
@@ -790,19 +821,14 @@ def _check_grouped(a, w, offsets, out=None, out_scale=None, *, out_dtype=None,
         raise ValueError(f"offsets is on {offsets.device}, the operands on {a.device}")
     if w.device != a.device:
         raise ValueError("operands on different devices")
-    if tile != "auto" and tile not in SCALED_TILES:
-        raise ValueError(f"a grouped GEMM is offered for tile auto / {SCALED_TILES}, not {tile!r} "
-                         "(the ping-pong, interleaved and 256x256 kernels have no grouped form)")
+    _check_tile(_GROUPED.noun, tile, _GROUPED.tile_note)
     fp4 = _is_fp4(a) or _is_fp4(w)
     fp8 = a.dtype == torch.float8_e4m3fn or w.dtype == torch.float8_e4m3fn
     if not fp4 and not fp8 and a.dtype not in (torch.bfloat16, torch.float16):
-        raise TypeError(f"a grouped GEMM takes bf16, f16, scaled fp8 or scaled fp4 operands, not "
-                        f"{a.dtype}")
-    if a.dtype != w.dtype:
-        raise TypeError(f"A dtype {a.dtype} != W dtype {w.dtype}")
+        _refuse_operands(_GROUPED, a)
+    _check_same_dtype(a, w)
     if (fp8 or fp4) and (a_scale is None or w_scale is None):
-        raise ValueError("a grouped GEMM on fp8 / fp4 operands needs a_scale and w_scale (the "
-                         "unit-scale kernels have no grouped form)")
+        raise ValueError(_GROUPED.no_scales)
     if w.stride(2) != 1 or w.stride(1) < w.shape[2] or (E > 1 and w.stride(0) < N * w.stride(1)):
         raise ValueError(f"w needs unit inner stride, rows of at least K and experts at least "
                          f"N rows apart (strides {tuple(w.stride())})")
@@ -823,45 +849,23 @@ def _check_grouped(a, w, offsets, out=None, out_scale=None, *, out_dtype=None,
         raise TypeError(f"block scales need fp8 / fp4 operands, not {a.dtype}")
     if out_quant is None and out_scale is not None:
         raise ValueError("out_scale goes with out_quant")
-    if T >= 2 ** 31 or N >= 2 ** 31 or K >= 2 ** 31:
-        raise ValueError("dimensions must fit in 32 bits")
+    _check_32_bits(T, N, K)
     # what the ungrouped forms refuse, per expert slice (all slices share shape and strides; the
     # first and the last differ in their addresses)
+    if not glu and out_quant is None:
+        _check_k(a, w)
     odt = None
     for g in sorted({0, E - 1}):
-        wg, wsg = w[g], (w_scale[g] if w_scale is not None else None)
+        kw = dict(out_dtype=out_dtype, a_scale=a_scale, tile=tile,
+                  w_scale=w_scale[g] if w_scale is not None else None)
         if glu:
-            odt = _check_glu(a, wg, out, out_scale, out_quant=out_quant, out_dtype=out_dtype,
-                             a_scale=a_scale, w_scale=wsg, tile=tile, act=act)[3]
+            odt = _check_glu(a, w[g], out, out_scale, out_quant=out_quant, act=act, **kw)[3]
         elif out_quant is not None:
-            _check_out_quant(a, wg, out_quant, out, out_scale, a_scale=a_scale, w_scale=wsg,
-                             tile=tile, out_dtype=out_dtype)
+            _check_out_quant(a, w[g], out_quant, out, out_scale, **kw)
             odt = out_quant_dtype(out_quant)
         else:
-            if a.shape[1] != wg.shape[1]:
-                raise ValueError(f"K mismatch: A {tuple(a.shape)} vs W {tuple(w.shape)}")
-            if scaled:
-                dense = (torch.bfloat16, torch.float16, torch.float32)
-                _check_block_scaled(_MX_FP4 if fp4 else _MX_FP8, a, wg, a_scale, wsg, T, tile,
-                                    "auto", 0, 0)
-            else:
-                if a_scale is not None or w_scale is not None:
-                    raise TypeError(f"block scales need fp8 / fp4 operands, not {a.dtype}")
-                dense = (a.dtype, torch.float32)
-            odt = out.dtype if out is not None else (out_dtype or dense[0])
-            if out is not None and out_dtype is not None and out_dtype != out.dtype:
-                raise TypeError(f"out is {out.dtype}, out_dtype={out_dtype}")
-            if odt not in dense:
-                raise TypeError(f"a grouped GEMM on {a.dtype} operands writes one of {dense}, "
-                                f"not {odt}")
-            if out is not None:
-                if out.device != a.device:
-                    raise ValueError(f"out is on {out.device}, the operands on {a.device}")
-                if out.dim() != 2 or out.shape[0] < T or out.shape[1] != N:
-                    raise ValueError(f"out must have shape (>= {T}, {N}), not {tuple(out.shape)}")
-                if out.stride(1) != 1 or out.stride(0) < N:
-                    raise ValueError(f"out needs unit inner stride and a row stride of at least "
-                                     f"{N} (strides {tuple(out.stride())})")
+            odt = _check_tiled(_GROUPED, a, w[g], out, None, out_quant=None, mode="auto", M=None,
+                               a_grp=0, c_grp=0, ksplit=0, **kw).odt
     return T, N, K, E, odt
 
 
@@ -886,53 +890,30 @@ def gemm_grouped(a, w, offsets, out=None, *, out_dtype=None, tile: str = "auto",
     Rows outside ``[o'[0], o'[E])`` are not written: they are unspecified in an ``out`` (and
     ``out_scale``) allocated here, which is never zero-filled, and untouched in one passed in.
     :func:`_check_grouped` holds every refusal."""
-    import torch
-
     T, N, K, E, odt = _check_grouped(a, w, offsets, out, out_scale, out_dtype=out_dtype,
                                      tile=tile, act=act, a_scale=a_scale, w_scale=w_scale,
                                      out_quant=out_quant, glu=glu)
-    C = load()
-    _check_placement(a)
-    if w.device.type != "cuda":
-        raise ValueError("native GEMM operands must be ROCm device tensors")
-    fp4, q4 = _is_fp4(a), out_quant == "mxfp4"
-    cols = N // 2 if glu else N
-    if out is None and out_quant is not None:
-        out = torch.empty((T, cols // 2 if q4 else cols), dtype=torch.uint8,
-                          device=a.device).view(odt)
-    elif out is None:
-        out = torch.empty((T, cols), dtype=odt, device=a.device)
-    if out_quant is not None and out_scale is None:
-        out_scale = torch.empty((T, cols // 32), dtype=torch.uint8, device=a.device)
-    _check_placement(out)
-    kb = K // 2 if fp4 else K  # the operands as the byte / element matrices the kernel reads
-    if T and N and not C.gemm_fast_path_ok(a.data_ptr(), w.data_ptr(), out.data_ptr(),
-                                           a.stride(0), w.stride(1), out.stride(0), T, N, kb,
-                                           DT_U8 if fp4 else dtype_code(a.dtype),
-                                           DT_U8 if out_quant else dtype_code(odt)):
-        raise ValueError("a grouped GEMM needs the MFMA fast path: 16-byte-aligned operand rows, "
-                         "8-byte-aligned output rows and K a whole number of 128-byte K-tiles")
-    s = stream if stream is not None else torch.cuda.current_stream(a.device).cuda_stream
-    am, cm = (2 if fp4 else 1), (2 if _is_fp4(out) else 1)
+    am = 2 if _is_fp4(a) else 1
     scaled = a_scale is not None
-    C.gemm_grouped(
-        a=a.data_ptr(), b=w.data_ptr(), c=out.data_ptr(), offs=offsets.data_ptr(), ngroups=E,
-        lda=am * a.stride(0), ldb=am * w.stride(1), ldc=cm * out.stride(0),
-        b_gstride=am * w.stride(0), M=T, N=N, K=K,
-        din=DT_FP4 if fp4 else dtype_code(a.dtype),
-        dout=DT_FP4 if cm == 2 else dtype_code(out.dtype), tile=TILES[tile], stream=s,
-        act=ACTS[act], a_scale=a_scale.data_ptr() if scaled else 0,
-        b_scale=w_scale.data_ptr() if scaled else 0,
-        a_scale_ld=a_scale.stride(0) if scaled else 0,
-        b_scale_ld=w_scale.stride(1) if scaled else 0,
-        b_scale_gstride=w_scale.stride(0) if scaled else 0,
-        c_scale=out_scale.data_ptr() if out_scale is not None else 0,
-        c_scale_ld=out_scale.stride(0) if out_scale is not None else 0, glu=1 if glu else 0)
-    if stream is not None:  # the outputs stay allocated until that stream reaches them
-        out.record_stream(torch.cuda.ExternalStream(s))
-        if out_scale is not None:
-            out_scale.record_stream(torch.cuda.ExternalStream(s))
-    return out if out_quant is None else (out[:T], out_scale[:T])
+
+    def launch(C, out, out_scale, s):
+        cm = 2 if _is_fp4(out) else 1
+        C.gemm_grouped(
+            a=a.data_ptr(), b=w.data_ptr(), c=out.data_ptr(), offs=offsets.data_ptr(), ngroups=E,
+            lda=am * a.stride(0), ldb=am * w.stride(1), ldc=cm * out.stride(0),
+            b_gstride=am * w.stride(0), M=T, N=N, K=K,
+            din=DT_FP4 if am == 2 else dtype_code(a.dtype),
+            dout=DT_FP4 if cm == 2 else dtype_code(out.dtype), tile=TILES[tile], stream=s,
+            act=ACTS[act], a_scale=a_scale.data_ptr() if scaled else 0,
+            b_scale=w_scale.data_ptr() if scaled else 0,
+            a_scale_ld=a_scale.stride(0) if scaled else 0,
+            b_scale_ld=w_scale.stride(1) if scaled else 0,
+            b_scale_gstride=w_scale.stride(0) if scaled else 0,
+            c_scale=out_scale.data_ptr() if out_scale is not None else 0,
+            c_scale_ld=out_scale.stride(0) if out_scale is not None else 0, glu=1 if glu else 0)
+
+    return _run_tiled(_GROUPED, _Tiled(T, N, K, odt), a, w, out, out_scale, launch,
+                      out_quant=out_quant, glu=glu, stream=stream)
 
 
 # ---------------------------------------------------------------- K-grouped GEMM (routed wgrad)
@@ -969,36 +950,25 @@ def _check_kgrouped(a, w, offsets, rows, out=None, *, a_scale=None, w_scale=None
     fp8 = a.dtype == torch.float8_e4m3fn or w.dtype == torch.float8_e4m3fn
     if not fp4 and not fp8:
         raise TypeError(f"a K-grouped GEMM takes block-scaled fp8 or fp4 operands, not {a.dtype}")
-    if a.dtype != w.dtype:
-        raise TypeError(f"A dtype {a.dtype} != W dtype {w.dtype}")
+    _check_same_dtype(a, w)
     if a_scale is None or w_scale is None:
-        raise ValueError("a K-grouped GEMM needs a_scale and w_scale (the unit-scale kernels have "
-                         "no K-grouped form)")
-    if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int32:
-        raise TypeError(f"offsets must be an int32 tensor, not "
-                        f"{getattr(offsets, 'dtype', type(offsets))}")
+        raise ValueError(_KGROUPED.no_scales)
+    _check_offsets_dtype(offsets)
     if offsets.dim() != 1 or not offsets.is_contiguous():
         raise ValueError(f"offsets must be contiguous and 1-D, not {tuple(offsets.shape)}")
     E = offsets.shape[0] - 1
-    if E < 1:
-        raise ValueError("a K-grouped GEMM needs at least one group")
-    if E > MAX_GROUPS:
-        raise ValueError(f"a K-grouped GEMM takes at most {MAX_GROUPS} groups, not {E}")
+    _check_group_count(_KGROUPED, E)
     if offsets.device != a.device or w.device != a.device:
         raise ValueError("operands and offsets on different devices")
     if not isinstance(rows, int) or isinstance(rows, bool) or rows < 0 or rows >= 2 ** 31:
         raise ValueError(f"rows (the bound the offsets are clamped to) must be an int in "
                          f"[0, 2^31), not {rows!r}")
-    if tile != "auto" and tile not in SCALED_TILES:
-        raise ValueError(f"a K-grouped GEMM is offered for tile auto / {SCALED_TILES}, not "
-                         f"{tile!r}")
+    _check_tile(_KGROUPED.noun, tile)
     f = _MX_FP4 if fp4 else _MX_FP8
     M, N = a.shape[0], w.shape[0]
     K = f.per_byte * a.shape[1]
-    if a.shape[1] != w.shape[1]:
-        raise ValueError(f"K mismatch: A {tuple(a.shape)} vs W {tuple(w.shape)}")
-    if M >= 2 ** 31 or N >= 2 ** 31 or K >= 2 ** 31:
-        raise ValueError("dimensions must fit in 32 bits")
+    _check_k(a, w)
+    _check_32_bits(M, N, K)
     cap = kgrouped_capacity(rows, E, f.kmod)
     if K < cap:
         raise ValueError(f"the operands have {K} columns, below the capacity {cap} of the padded "
@@ -1007,23 +977,8 @@ def _check_kgrouped(a, w, offsets, rows, out=None, *, a_scale=None, w_scale=None
         if t.stride(1) != 1 or t.stride(0) < t.shape[1]:
             raise ValueError(f"{name} needs unit inner stride (strides {tuple(t.stride())})")
     _check_block_scaled(f, a, w, a_scale, w_scale, M, tile, "auto", 0, 0)
-    dense = (torch.bfloat16, torch.float16, torch.float32)
-    odt = out.dtype if out is not None else (out_dtype or torch.bfloat16)
-    if out is not None and out_dtype is not None and out_dtype != out.dtype:
-        raise TypeError(f"out is {out.dtype}, out_dtype={out_dtype}")
-    if odt not in dense:
-        raise TypeError(f"a K-grouped GEMM writes one of {dense}, not {odt}")
-    if out is not None:
-        if out.device != a.device:
-            raise ValueError(f"out is on {out.device}, the operands on {a.device}")
-        if out.dim() != 3 or tuple(out.shape) != (E, M, N):
-            raise ValueError(f"out must have shape {(E, M, N)}, not {tuple(out.shape)}")
-        if out.stride(2) != 1 or out.stride(1) < N or \
-                (E > 1 and out.stride(0) < M * out.stride(1)):
-            raise ValueError(f"out needs unit inner stride, rows of at least N and groups at "
-                             f"least M rows apart (strides {tuple(out.stride())})")
-        if out.stride(0) * out.element_size() % 8:
-            raise ValueError("the groups' outputs must be a multiple of 8 bytes apart")
+    odt = _check_dense_out(_KGROUPED.noun, a, out, out_dtype,
+                           (torch.bfloat16, torch.float16, torch.float32), M, N, groups=E)
     return M, N, K, E, odt
 
 
@@ -1044,33 +999,16 @@ def gemm_kgrouped(a, w, offsets, rows, out=None, *, a_scale, w_scale, out_dtype=
     ``out[g]`` is bit for bit what ``gemm`` with the same tile writes for those column slices, and
     a group without rows gets ``+0.0`` everywhere. Tiles :data:`SCALED_TILES`.
     :func:`_check_kgrouped` holds every refusal."""
-    import torch
-
     M, N, K, E, odt = _check_kgrouped(a, w, offsets, rows, out, a_scale=a_scale, w_scale=w_scale,
                                       out_dtype=out_dtype, tile=tile)
-    C = load()
-    _check_placement(a)
-    if w.device.type != "cuda":
-        raise ValueError("native GEMM operands must be ROCm device tensors")
-    if out is None:
-        out = torch.empty((E, M, N), dtype=odt, device=a.device)
-    _check_placement(out[0])
-    fp4 = _is_fp4(a)
-    if M and N and not C.gemm_fast_path_ok(a.data_ptr(), w.data_ptr(), out.data_ptr(),
-                                           a.stride(0), w.stride(0), out.stride(1), M, N,
-                                           K // 2 if fp4 else K,
-                                           DT_U8 if fp4 else dtype_code(a.dtype),
-                                           dtype_code(odt)):
-        raise ValueError("a K-grouped GEMM needs the MFMA fast path: 16-byte-aligned operand "
-                         "rows, 8-byte-aligned output rows")
-    s = stream if stream is not None else torch.cuda.current_stream(a.device).cuda_stream
-    am = 2 if fp4 else 1
-    C.gemm_kgrouped(
-        a=a.data_ptr(), b=w.data_ptr(), c=out.data_ptr(), offs=offsets.data_ptr(), ngroups=E,
-        rows=rows, lda=am * a.stride(0), ldb=am * w.stride(0), ldc=out.stride(1),
-        c_gstride=out.stride(0), M=M, N=N, K=K, din=DT_FP4 if fp4 else dtype_code(a.dtype),
-        dout=dtype_code(odt), tile=TILES[tile], stream=s, a_scale=a_scale.data_ptr(),
-        b_scale=w_scale.data_ptr(), a_scale_ld=a_scale.stride(0), b_scale_ld=w_scale.stride(0))
-    if stream is not None:  # the output stays allocated until that stream reaches it
-        out.record_stream(torch.cuda.ExternalStream(s))
-    return out
+    am = 2 if _is_fp4(a) else 1
+    return _run_tiled(
+        _KGROUPED, _Tiled(M, N, K, odt), a, w, out, None,
+        lambda C, out, _, s: C.gemm_kgrouped(
+            a=a.data_ptr(), b=w.data_ptr(), c=out.data_ptr(), offs=offsets.data_ptr(), ngroups=E,
+            rows=rows, lda=am * a.stride(0), ldb=am * w.stride(0), ldc=out.stride(1),
+            c_gstride=out.stride(0), M=M, N=N, K=K,
+            din=DT_FP4 if am == 2 else dtype_code(a.dtype), dout=dtype_code(odt),
+            tile=TILES[tile], stream=s, a_scale=a_scale.data_ptr(), b_scale=w_scale.data_ptr(),
+            a_scale_ld=a_scale.stride(0), b_scale_ld=w_scale.stride(0)),
+        groups=E, stream=stream)

@@ -333,6 +333,23 @@ int main() {
       if (pt.apply(c)) run(f.name, "8192x1024x512", "auto", pt.name, c);
     }
   }
+  // an empty problem with one malformed shape argument, for fp4 operands and quantised outputs
+  for (const Family& f : kFamilies) {
+    const bool in4 = f.din == DT_FP4;
+    if (!in4 && !f.c_scale) continue;
+    for (const char* empty : {"M=0", "N=0"}) {
+      for (const char* fault : {"K=384", "lda=K+1", "lda<K", "ldb<K"}) {
+        const std::string what = std::string(empty) + "_" + fault;
+        if (!in4 && (what.find("K=384") != std::string::npos || what.find("K+1") != std::string::npos))
+          continue;  // rules of fp4 operands: K % 256, even leading dimensions
+        Case c = base_case(f, 256, 256, 512, TILE_AUTO);
+        (empty[0] == 'M' ? c.p.M : c.p.N) = 0;
+        for (const Perturbation& pt : perts)
+          if (fault == std::string(pt.name)) pt.apply(c);
+        run(f.name, "256x256x512", "auto", what.c_str(), c);
+      }
+    }
+  }
   fflush(stdout);
   return ferror(stdout) ? 1 : 0;
 }

@@ -248,6 +248,20 @@ static std::vector<Perturbation> perturbations() {
   return v;
 }
 
+// An empty problem (M == 0 or N == 0) with one malformed shape argument is refused: the rules on the
+// shape come before the empty problem's hipSuccess.
+struct EmptyFault {
+  const char* name;
+  std::function<bool(Case&)> apply;  // false: does not apply to this form
+};
+static const EmptyFault kEmptyFaults[] = {
+    {"fp4 K % 256", [](Case& c) {
+       if (c.din != DT_FP4) return false; c.p.K = c.p.lda = c.p.ldb = 384; return true; }},
+    {"fp4 odd lda", [](Case& c) { if (c.din != DT_FP4) return false; c.p.lda += 1; return true; }},
+    {"lda < K", [](Case& c) { c.p.lda = c.p.K - 16; return true; }},
+    {"ldb < K", [](Case& c) { c.p.ldb = c.p.K - 16; return true; }},
+};
+
 int main() {
   static const int tiles[] = {TILE_AUTO, TILE_256x128, TILE_128x256, TILE_128x128,
                               TILE_256x128_W4};
@@ -277,6 +291,13 @@ int main() {
       Case z = base_case(f, 256, 1024, 512, TILE_AUTO);
       (which ? z.p.N : z.p.M) = 0;
       CHECK(launch(z) == hipSuccess && g_launches.empty(), "%s: empty problem", f.name);
+      for (const EmptyFault& ef : kEmptyFaults) {
+        Case y = z;
+        if (!ef.apply(y)) continue;
+        const hipError_t e = launch(y);
+        CHECK(e == hipErrorInvalidValue && g_launches.empty(), "%s: empty problem (%s = 0) with %s: %d",
+              f.name, which ? "N" : "M", ef.name, (int)e);
+      }
     }
   }
   const std::vector<Perturbation> perts = perturbations();
