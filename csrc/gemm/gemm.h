@@ -1,4 +1,15 @@
 // Public interface of the CDNA4 MFMA GEMM (csrc/gemm/gemm_mfma.hip).
+//
+// Non-finite values (every kernel and launch form; tests/test_nonfinite_gpu.py). The GEMM is
+// IEEE 754 per element: an output element is NaN if any product of its dot is NaN (a NaN
+// operand, Inf x 0, or +Inf and -Inf products both present), otherwise +-Inf if an infinite
+// product is present, otherwise the sum, rounded once to the output dtype; a K-split keeps this
+// through its partials and the reduce kernel. Elements outside a view (row padding, skipped
+// grouped rows, columns no group owns) never influence anything, whatever bits they hold. The
+// epilogue activations equal the f32 reference in class: relu(NaN) is NaN, gelu and silu give
+// NaN at NaN and -Inf and +Inf at +Inf. A block-scale byte 255 (the E8M0 NaN) makes every
+// product of its block NaN. The quantising epilogue and the MX quantisers below never hide a
+// non-finite value: mx_cvt.h has the rule.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -249,6 +260,8 @@ enum AgMode : int {
 // q[R, K] e4m3 (rows ldq bytes apart) and s[R, K / 32] E8M0 bytes (rows lds bytes apart), one
 // scale per 32 consecutive K elements: the smallest power of two 2^e with amax / 2^e <= 448
 // (e clamped to [-127, 127], an all-zero block gets e = 0), s = e + 127, q = rne(x / 2^e).
+// amax is taken over the finite elements; a NaN or +-Inf element becomes the e4m3fn NaN byte
+// with its sign (fp4: the nibble 0x7 | sign << 3, and its block's scale byte 255).
 // K % 128 == 0; x rows 16-byte and q rows 8-byte aligned (checked by the caller, and here).
 struct MxQuantArgs {
   const void* x = nullptr;

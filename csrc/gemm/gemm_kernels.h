@@ -188,7 +188,7 @@ __device__ __forceinline__ float act1(float x, int act) {
       const float u = 0.7978845608028654f * (x + 0.044715f * x * x * x);
       return x_sigmoid(x, 2.f * u);
     }
-    case ACT_RELU: return x > 0.f ? x : 0.f;
+    case ACT_RELU: return x <= 0.f ? 0.f : x;  // (NaN fails the compare and stays NaN)
     case ACT_SILU: return x_sigmoid(x, x);
     default: return x;
   }
@@ -708,13 +708,11 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_tn_kernel(const GemmArgs p) 
         unsigned m = 0;
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
-          const unsigned u = mx_abs_bits(v[r]);
-          m = u > m ? u : m;
+          m = mx_amax_join<Q4>(m, mx_amax_bits<Q4>(v[r]));
         }
 #pragma unroll
         for (int d = 16; d <= 32; d *= 2) {
-          const unsigned o = (unsigned)__shfl_xor((int)m, d);
-          m = o > m ? o : m;
+          m = mx_amax_join<Q4>(m, (unsigned)__shfl_xor((int)m, d));
         }
         const int e = mx_scale_exp<Q4>(m);
         if constexpr (Q4) {
@@ -736,7 +734,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_tn_kernel(const GemmArgs p) 
             *(unsigned*)(crow + col + 16 + fq * 4) = w1;
           }
         }
-        if (ok && fq == 0) srow[col / 32] = (uint8_t)(e + 127);
+        if (ok && fq == 0) srow[col / 32] = (uint8_t)mx_scale_byte<Q4>(m, e);
       };
       if constexpr (GLU) {
         // Gated: a wave's 64 columns are 32 gate and the 32 matching up columns, fragments 4b,

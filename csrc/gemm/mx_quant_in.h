@@ -70,13 +70,11 @@ __device__ __forceinline__ void mxq_rowwise_vec(const mxq_u32x4 v, char* q, uint
   unsigned m = 0;  // |x| as an integer: ordered as the floats are
 #pragma unroll
   for (int i = 0; i < EPV; ++i) {
-    const unsigned b = mx_abs_bits(f[i]);
-    m = b > m ? b : m;
+    m = mx_amax_join<FP4>(m, mx_amax_bits<FP4>(f[i]));
   }
 #pragma unroll
   for (int d = 1; d < LPB; d *= 2) {
-    const unsigned o = (unsigned)__shfl_xor((int)m, d);
-    m = o > m ? o : m;
+    m = mx_amax_join<FP4>(m, (unsigned)__shfl_xor((int)m, d));
   }
   const int e = mx_scale_exp<FP4>(m);  // (mx_cvt.h: the rule, shared with the GEMM epilogue)
   if constexpr (FP4) {
@@ -101,7 +99,7 @@ __device__ __forceinline__ void mxq_rowwise_vec(const mxq_u32x4 v, char* q, uint
     else
       *(unsigned*)q = out[0];
   }
-  if (lead) *s = (uint8_t)(e + 127);
+  if (lead) *s = (uint8_t)mx_scale_byte<FP4>(m, e);
 }
 
 }  // namespace ddlb

@@ -96,8 +96,7 @@ void mx_quant_t_grouped_kernel(const MxQuantTGroupedArgs a, int ctiles) {
 #pragma unroll
     for (int i = 0; i < 32; ++i) {
       f[i] = In::elem(p + i * VPR * 16);
-      const unsigned ab = mx_abs_bits(f[i]);
-      m = ab > m ? ab : m;
+      m = mx_amax_join<FP4>(m, mx_amax_bits<FP4>(f[i]));
     }
     const int e = mx_scale_exp<FP4>(m);
     const int col = c0 + c;
@@ -129,7 +128,7 @@ void mx_quant_t_grouped_kernel(const MxQuantTGroupedArgs a, int ctiles) {
       }
     }
     // four neighbouring blocks' scale bytes -> one aligned 32-bit word (NB % 4 == 0)
-    unsigned sw = (unsigned)(e + 127) << (8 * (b & 3));
+    unsigned sw = mx_scale_byte<FP4>(m, e) << (8 * (b & 3));
     sw |= (unsigned)__shfl_xor((int)sw, 1);
     sw |= (unsigned)__shfl_xor((int)sw, 2);
     if (ok && (b & 3) == 0)

@@ -11,9 +11,19 @@ The quantisation rule rounds the scale UP, so nothing saturates. Per block, in f
 ``amax / 2^e <= 448``, the largest e4m3 value), clamped to [-127, 127]; ``s = e + 127`` and
 ``q = e4m3_rne(clamp(x 2^-e, -448, 448))``. ``s = 255`` is never produced. The sign of a zero is
 kept: -0, and a negative value that rounds to zero, give the byte 0x80 (kernel and reference
-agree byte for byte, ``tests/test_mx_extremes_gpu.py``). Non-finite input is unspecified. (The
-OCP "floor" rule, ``e = floor(log2 amax) - 8``, would clamp every element above 448 2^e: 11 % of
-the elements of U[-1, 1) data.)
+agree byte for byte, ``tests/test_mx_extremes_gpu.py``). (The OCP "floor" rule,
+``e = floor(log2 amax) - 8``, would clamp every element above 448 2^e: 11 % of the elements of
+U[-1, 1) data.)
+
+Non-finite input (all seven producers: the three row quantisers, the transposing, two-way and
+grouped transposing ones, and the GEMM's quantising epilogue; ``tests/test_nonfinite_gpu.py``).
+``amax`` is taken over the finite elements only: a NaN or +-Inf element counts as 0, and a block
+with no finite non-zero element gets ``s = 127``. The finite elements are quantised exactly as
+without it; no byte of an all-finite block depends on this paragraph. A NaN or +-Inf element
+becomes the e4m3fn NaN byte with the input's sign, ``0x7F | sign << 7`` (e4m3fn has no Inf; it is
+what torch's own cast gives). The reference builds these bytes itself (``torch.where`` on
+``~isfinite``) and relies on no device's cast. An upstream overflow or NaN therefore stays visible:
+the scaled GEMM that reads the block returns NaN for that row (or column).
 
 :func:`quantize_mx_reference` and :func:`dequantize_mx` are pure torch, run on any device, and are
 the specification; :func:`quantize_mx` is the HIP kernel (``csrc/gemm/mx_quant.hip``).
@@ -29,6 +39,16 @@ with ties to the even code (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2
 5 -> 4). The input's sign bit is kept (-0 and a negative value that rounds to zero give 0x8).
 :func:`quantize_mxfp4_reference` / :func:`dequantize_mxfp4` are the specification,
 :func:`quantize_mxfp4` the HIP kernel.
+
+Non-finite input in MXFP4. E2M1 has no NaN; the format's only NaN is the scale byte 255, and in
+the OCP rule every element of such a block is NaN. The block-scaled MFMA of gfx950 follows it:
+with one ``a_scale`` byte set to 255 the output row is NaN in every column, zero-valued elements
+and an all-zero block included, for every tile code, MX-fp8 and MXFP4 alike (measured,
+``test_scale_byte_255``; docs/RESULTS.md). So a block that holds any NaN or +-Inf element gets
+``s = 255``; its finite elements are quantised by the finite-amax rule above and each non-finite
+element gets the nibble ``0x7 | sign << 3``. :func:`dequantize_mx` and :func:`dequantize_mxfp4`
+return NaN for every element of a block with ``s = 255``. MX-fp8 never produces ``s = 255``; an
+all-finite MXFP4 block never does either.
 """
 
 from __future__ import annotations
@@ -71,13 +91,27 @@ def quantize_mx_reference(x):
     _check_2d(x)
     R, K = x.shape
     xb = x.to(torch.float32).reshape(R, K // BLOCK, BLOCK)
-    amax = xb.abs().amax(dim=2)
+    finite = torch.isfinite(xb)
+    xf = torch.where(finite, xb, torch.zeros_like(xb))  # a non-finite element counts as 0
+    amax = xf.abs().amax(dim=2)
     m, ex = torch.frexp(amax)
     e = torch.where(m <= 0.875, ex - 9, ex - 8).clamp(-127, 127)
     e = torch.where(amax == 0, torch.zeros_like(e), e)
     # the clamp stays: torch's own e4m3 cast turns values above 464 into NaN
-    y = ldexp_exact(xb, (-e).unsqueeze(2)).clamp(-E4M3_MAX, E4M3_MAX)
-    return y.to(torch.float8_e4m3fn).reshape(R, K), (e + 127).to(torch.uint8)
+    y = ldexp_exact(xf, (-e).unsqueeze(2)).clamp(-E4M3_MAX, E4M3_MAX)
+    # NaN and +-Inf: the e4m3fn NaN byte with the input's sign, built here (no device's cast)
+    sign = (xb.view(torch.int32) >> 31) & 1
+    q = torch.where(finite, y.to(torch.float8_e4m3fn).view(torch.uint8),
+                    (0x7F | (sign << 7)).to(torch.uint8))
+    return q.view(torch.float8_e4m3fn).reshape(R, K), (e + 127).to(torch.uint8)
+
+
+def _nan_blocks(v, s):
+    """``v [R, K / 32, 32]`` with every element of a block whose scale byte is 255 (the E8M0 NaN)
+    set to NaN, zeros included, as the block-scaled MFMA treats it."""
+    import torch
+
+    return torch.where((s == 255).unsqueeze(2), torch.full_like(v, float("nan")), v)
 
 
 def dequantize_mx(q, s):
@@ -93,8 +127,8 @@ def dequantize_mx(q, s):
     if tuple(s.shape) != (R, K // BLOCK):
         raise ValueError(f"scales must have shape {(R, K // BLOCK)}, not {tuple(s.shape)}")
     e = s.to(torch.int32) - 127
-    return ldexp_exact(q.to(torch.float32).reshape(R, K // BLOCK, BLOCK),
-                       e.unsqueeze(2)).reshape(R, K)
+    v = ldexp_exact(q.to(torch.float32).reshape(R, K // BLOCK, BLOCK), e.unsqueeze(2))
+    return _nan_blocks(v, s).reshape(R, K)
 
 
 def _quantize_rows(x, fp4: bool, stream):
@@ -168,14 +202,19 @@ def quantize_mxfp4_reference(x):
     _check_2d_fp4(x)
     R, K = x.shape
     xb = x.to(torch.float32).reshape(R, K // BLOCK, BLOCK)
-    amax = xb.abs().amax(dim=2)
+    finite = torch.isfinite(xb)
+    xf = torch.where(finite, xb, torch.zeros_like(xb))  # a non-finite element counts as 0
+    amax = xf.abs().amax(dim=2)
     m, ex = torch.frexp(amax)
     e = torch.where(m <= 0.75, ex - 3, ex - 2).clamp(-127, 127)
     e = torch.where(amax == 0, torch.zeros_like(e), e)
-    y = ldexp_exact(xb, (-e).unsqueeze(2))
+    y = ldexp_exact(xf, (-e).unsqueeze(2))
     code = _e2m1_code(y.abs().clamp(max=E2M1_MAX))
+    code = torch.where(finite, code, torch.full_like(code, 7))  # NaN, +-Inf: the nibble 0x7 | sign
     sign = (xb.view(torch.int32) >> 31) & 1  # the input's sign bit: -0 stays negative
-    return pack_e2m1(((sign << 3) | code).reshape(R, K)), (e + 127).to(torch.uint8)
+    # a block that holds a non-finite element: the E8M0 NaN byte
+    s = torch.where(finite.all(dim=2), e + 127, torch.full_like(e, 255))
+    return pack_e2m1(((sign << 3) | code).reshape(R, K)), s.to(torch.uint8)
 
 
 def pack_e2m1(nib):
@@ -213,7 +252,8 @@ def dequantize_mxfp4(q, s):
     if K % BLOCK or tuple(s.shape) != (R, K // BLOCK):
         raise ValueError(f"scales must have shape {(R, K // BLOCK)}, not {tuple(s.shape)}")
     e = s.to(torch.int32) - 127
-    return ldexp_exact(unpack_e2m1(q).reshape(R, K // BLOCK, BLOCK), e.unsqueeze(2)).reshape(R, K)
+    v = ldexp_exact(unpack_e2m1(q).reshape(R, K // BLOCK, BLOCK), e.unsqueeze(2))
+    return _nan_blocks(v, s).reshape(R, K)
 
 
 def quantize_mxfp4(x, *, stream=None):

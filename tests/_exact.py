@@ -118,6 +118,113 @@ def extreme_scales(M, N, K, gen):
     return (e_a + 127).to(torch.uint8), (e_w + 127).to(torch.uint8), e_a, e_w
 
 
+# ---------------------------------------------------------------------------- non-finite values
+# The padding of an operand as a caching allocator can leave it: a value that a kernel which loads
+# it and multiplies it by a masked zero turns into NaN (POISON x 0 is 0). NaN for the float
+# dtypes; the e4m3 NaN byte; 6.0 pairs for packed fp4 data (E2M1 has no NaN); the NaN scale byte.
+NONFINITE_POISON = {torch.bfloat16: float("nan"), torch.float16: float("nan"),
+                    torch.float32: float("nan"), torch.float64: float("nan"),
+                    FP8: 0x7F, "fp4": 0x77, "scale": 255}
+
+
+def nan_padded(x, kind=None, **kw):
+    """:func:`padded` with ``NONFINITE_POISON`` around the view. ``kind`` names the entry for byte
+    arrays (``"fp4"``, ``"scale"``); e4m3 and the byte arrays are filled as bytes."""
+    key = kind if kind is not None else x.dtype
+    fill = NONFINITE_POISON[key]
+    if isinstance(fill, float):
+        return padded(x, poison=fill, **kw)
+    raw = x.view(torch.uint8)
+    return padded(raw, poison=fill, **kw).view(x.dtype)
+
+
+def planted(a, w):
+    """Copies of the integer operands ``a [M, K]``, ``w [N, K]`` (M >= 8, N >= 6, K >= 8) with
+    non-finite values planted, each plant in a row or column of its own, and the places as a dict:
+    NaN in ``A[r0, 0]`` (first row tile, first K-tile), +Inf in ``A[r1 = M - 1, K - 1]`` (ragged
+    last row tile, last K-tile), +Inf and -Inf in two columns of ``A[r2]``, NaN in
+    ``W[n0, K // 2]``, -Inf in ``W[n1 = N - 1, 0]`` (the scalar column tail). The partner column
+    of every Inf is made to hold a negative, a zero and a positive value, so the output row (or
+    column) of that Inf holds -Inf, NaN and +Inf. fp8 operands (no Inf in e4m3fn) take only the
+    NaN bytes: 0x7F in A, 0xFF in W."""
+    M, K = a.shape
+    N = w.shape[0]
+    assert M >= 8 and N >= 6 and K >= 8
+    a, w = a.clone(), w.clone()
+    p = dict(r0=1, r1=M - 1, r2=M // 2, n0=2, n1=N - 1, k2p=3, k2m=K - 2)
+    if a.dtype == FP8:
+        a.view(torch.uint8)[p["r0"], 0] = 0x7F
+        w.view(torch.uint8)[p["n0"], K // 2] = 0xFF
+        return a, w, p
+    inf, nan = float("inf"), float("nan")
+    # the partner columns: W[:, K-1], W[:, k2p], W[:, k2m] (rows n0, n1 keep their own plants'
+    # columns K // 2 and 0 untouched) and A[:, 0]
+    for col in (K - 1, p["k2p"], p["k2m"]):
+        w[0, col], w[1, col], w[3, col] = -1.0, 0.0, 2.0
+    a[0, 0], a[2, 0], a[3, 0] = -2.0, 0.0, 1.0
+    a[p["r0"], 0] = nan
+    a[p["r1"], K - 1] = inf
+    a[p["r2"], p["k2p"]] = inf
+    a[p["r2"], p["k2m"]] = -inf
+    w[p["n0"], K // 2] = nan
+    w[p["n1"], 0] = -inf
+    for col in (K - 1, p["k2p"], p["k2m"]):
+        c = w[:, col].float()
+        assert bool((c < 0).any()) and bool((c == 0).any()) and bool((c > 0).any())
+    c = a[:, 0].float()
+    assert bool((c < 0).any()) and bool((c == 0).any()) and bool((c > 0).any())
+    return a, w, p
+
+
+def classes64(a, w):
+    """The class rule of ``a @ w.T`` as a plain function, fp64 ``[M, N]``: an element is NaN when
+    any product of its dot is NaN (a NaN operand, Inf x 0, or +Inf and -Inf products both
+    present), otherwise +-Inf when an infinite product is present, otherwise the exact sum of the
+    finite products. Nothing here multiplies or adds a non-finite number: the classes come from
+    masks and counts, the sum from the operands' finite parts."""
+    A, W = a.to(torch.float32).double(), w.to(torch.float32).double()
+    fin_a, fin_w = torch.isfinite(A), torch.isfinite(W)
+    Af, Wf = torch.where(fin_a, A, 0.0), torch.where(fin_w, W, 0.0)
+    total = Af @ Wf.t()                                   # every non-finite element counted as 0
+
+    def cnt(x, y):                                        # pairs k with x[m, k] and y[n, k]
+        return x.double() @ y.double().t()
+
+    nan_a, nan_w = torch.isnan(A), torch.isnan(W)
+    inf_a, inf_w = torch.isinf(A), torch.isinf(W)
+    ones_a, ones_w = torch.ones_like(fin_a), torch.ones_like(fin_w)
+    is_nan = cnt(nan_a, ones_w) + cnt(ones_a, nan_w) > 0                  # a NaN operand
+    is_nan |= cnt(inf_a, fin_w & (W == 0)) + cnt(fin_a & (A == 0), inf_w) > 0   # Inf x 0
+    # the sign of an infinite product: sign(inf operand) x sign(partner), partner non-zero
+    pos_a, neg_a, pos_w, neg_w = A > 0, A < 0, W > 0, W < 0           # (NaN is neither)
+    infp_a, infm_a = inf_a & pos_a, inf_a & neg_a
+    infp_w, infm_w = inf_w & pos_w, inf_w & neg_w
+    # an infinite product needs an infinite operand on at least one side
+    n_pos = (cnt(infp_a, pos_w) + cnt(infm_a, neg_w)
+             + cnt(pos_a & fin_a, infp_w) + cnt(neg_a & fin_a, infm_w))
+    n_neg = (cnt(infp_a, neg_w) + cnt(infm_a, pos_w)
+             + cnt(pos_a & fin_a, infm_w) + cnt(neg_a & fin_a, infp_w))
+    is_nan |= (n_pos > 0) & (n_neg > 0)
+    out = total.clone()
+    out[n_pos > 0] = float("inf")
+    out[n_neg > 0] = float("-inf")
+    out[is_nan] = float("nan")
+    return out
+
+
+def same(got, want):
+    """Equal by class, then by value: the NaN masks are equal, and with every NaN set to 0 the
+    tensors are ``torch.equal`` (infinities compare by value and sign)."""
+    assert got.shape == want.shape and got.dtype == want.dtype, (got.shape, want.shape)
+    gn, wn = torch.isnan(got), torch.isnan(want)
+    bad = (gn != wn).nonzero()
+    assert bad.numel() == 0, f"NaN masks differ at {bad[:8].tolist()} ({bad.shape[0]} places)"
+    g0 = torch.nan_to_num(got.double(), nan=0.0, posinf=float("inf"), neginf=float("-inf"))
+    w0 = torch.nan_to_num(want.double(), nan=0.0, posinf=float("inf"), neginf=float("-inf"))
+    bad = (g0 != w0).nonzero()
+    assert bad.numel() == 0, f"values differ at {bad[:8].tolist()} ({bad.shape[0]} places)"
+
+
 # ---------------------------------------------------------------------------- far views
 FAR_GUARD = 2 ** 31
 SCAN_CHUNK = 256 << 20    # bytes per scanned piece

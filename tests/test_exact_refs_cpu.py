@@ -398,3 +398,115 @@ def test_fill_word():
     for dtype in (torch.bfloat16, torch.float16, FP8, torch.float32, torch.float64):
         w = torch.tensor([X.fill_word(POISON, dtype)], dtype=torch.int64).view(dtype)
         assert bool((w.to(torch.float64) == POISON).all())
+
+
+# ---------------------------------------------------------------------------- non-finite values
+def _loop_classes(a, w):
+    """The class rule as a Python triple loop over floats: every product is formed and classified
+    by itself, nothing non-finite is ever added."""
+    import math
+
+    A, W = a.to(torch.float32).tolist(), w.to(torch.float32).tolist()
+    out = []
+    for ra in A:
+        row = []
+        for rw in W:
+            nan = pos = neg = False
+            total = 0.0
+            for x, y in zip(ra, rw):
+                if math.isnan(x) or math.isnan(y) or (math.isinf(x) and y == 0) \
+                        or (math.isinf(y) and x == 0):
+                    nan = True
+                elif math.isinf(x) or math.isinf(y):
+                    if (x > 0) == (y > 0):
+                        pos = True
+                    else:
+                        neg = True
+                else:
+                    total += x * y
+            row.append(float("nan") if nan or (pos and neg) else float("inf") if pos
+                       else float("-inf") if neg else total)
+        out.append(row)
+    return torch.tensor(out, dtype=torch.float64)
+
+
+def test_classes64_against_loops_and_fp64_matmul():
+    nan, inf = float("nan"), float("inf")
+    g = _gen(41)
+    a, w = ints((7, 32), torch.float32, g), ints((5, 32), torch.float32, g)
+    a[0, 0] = nan
+    a[1, 31] = inf
+    a[2, 3], a[2, 30] = inf, -inf
+    a[3, 4] = -inf
+    a[4, 8], w[1, 8] = inf, -inf               # Inf x Inf
+    w[2, 16] = nan
+    w[4, 0] = -inf
+    w[0, 31], w[1, 31], w[3, 31] = -1.0, 0.0, 2.0
+    a[5, 0], a[6, 0] = 0.0, 2.0
+    got = X.classes64(a, w)
+    X.same(got, _loop_classes(a, w))
+    X.same(got, a.double() @ w.double().t())   # IEEE fp64 arithmetic has the same classes
+    assert bool(torch.isnan(got[0]).all()) and bool(torch.isnan(got[:, 2]).all())
+    assert bool((got == inf).any()) and bool((got == -inf).any())
+    assert bool(torch.isfinite(got).any())
+    fin = torch.isfinite(got)
+    assert torch.equal(got[fin], exact64(torch.nan_to_num(a, 0, 0, 0), torch.nan_to_num(w, 0, 0, 0))[fin])
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32, torch.float64,
+                                   FP8])
+def test_planted_puts_every_class_where_it_says(dtype):
+    M, N, K = 70, 11, 64
+    g = _gen(42)
+    a0, w0 = ints((M, K), dtype, g), ints((N, K), dtype, g)
+    a, w, p = X.planted(a0, w0)
+    assert p["r0"] < 128 and p["r1"] == M - 1 and p["n1"] == N - 1
+    assert len({p["r0"], p["r1"], p["r2"]}) == 3 and p["n0"] != p["n1"]
+    ref = X.classes64(a, w)
+    X.same(ref, _loop_classes(a, w))
+    assert bool(torch.isnan(ref[p["r0"]]).all()) and bool(torch.isnan(ref[:, p["n0"]]).all())
+    if dtype == FP8:                           # NaN bytes only: 0x7F in A, 0xFF in W
+        assert int(a.view(torch.uint8)[p["r0"], 0]) == 0x7F
+        assert int(w.view(torch.uint8)[p["n0"], K // 2]) == 0xFF
+        assert int((~torch.isfinite(ref)).sum()) == M + N - 1
+        return
+    inf = float("inf")
+    for line in (ref[p["r1"]], ref[p["r2"]], ref[:, p["n1"]]):
+        assert bool(torch.isnan(line).any())
+    for line in (ref[p["r1"]], ref[:, p["n1"]]):
+        assert bool((line == inf).any()) and bool((line == -inf).any())
+    clean = torch.ones((M, N), dtype=torch.bool)
+    clean[[p["r0"], p["r1"], p["r2"]]] = False
+    clean[:, [p["n0"], p["n1"]]] = False
+    assert bool(torch.isfinite(ref[clean]).all())
+
+
+def test_same_tells_classes_and_values_apart():
+    nan, inf = float("nan"), float("inf")
+    x = torch.tensor([[1.0, nan, inf, -inf, 0.0]])
+    X.same(x, x.clone())
+    for i, v in ((0, 2.0), (1, 0.0), (2, -inf), (3, nan), (2, 3.4e38), (4, nan)):
+        y = x.clone()
+        y[0, i] = v
+        with pytest.raises(AssertionError):
+            X.same(y, x)
+
+
+def test_nan_padded_fills_with_the_nonfinite_poison():
+    def whole(v):  # the [R + 3, ld] buffer behind the view
+        return torch.as_strided(v, (v.shape[0] + 3, v.stride(0)), (v.stride(0), 1), 0)
+
+    g = _gen(43)
+    for dt in (torch.bfloat16, torch.float16, torch.float32, torch.float64):
+        x = ints((5, 12), dt, g)
+        v = X.nan_padded(x)
+        assert torch.equal(v, x) and v.stride(0) > 12
+        assert int(torch.isnan(whole(v)).sum()) == 8 * v.stride(0) - 5 * 12
+    x = ints((5, 16), FP8, g)
+    v = X.nan_padded(x)
+    assert v.dtype == FP8 and torch.equal(v.view(torch.uint8), x.view(torch.uint8))
+    assert int((whole(v.view(torch.uint8)) == 0x7F).sum()) == 8 * v.stride(0) - 80
+    s = X.nan_padded(torch.full((5, 16), 127, dtype=torch.uint8), "scale")
+    assert int((whole(s) == 255).sum()) == 8 * s.stride(0) - 80
+    q = X.nan_padded(torch.zeros((5, 16), dtype=torch.uint8), "fp4")
+    assert int((whole(q) == 0x77).sum()) == 8 * q.stride(0) - 80
