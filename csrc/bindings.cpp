@@ -15,6 +15,7 @@
 
 #include "comm/comm.h"
 #include "gemm/gemm.h"
+#include "gemm/glu_act.h"
 #include "moe/moe.h"
 #include "moe/moe_route_map.h"
 #include "runtime/kernels.h"
@@ -308,6 +309,56 @@ PYBIND11_MODULE(_C, m) {
         py::arg("y"), py::arg("slot_row"), py::arg("gate"), py::arg("out"), py::arg("ldy"),
         py::arg("ldo"), py::arg("S"), py::arg("k"), py::arg("T"), py::arg("H"), py::arg("din"),
         py::arg("dout"), py::arg("stream") = 0);
+  m.def("moe_gather",
+        [](uintptr_t x, uintptr_t row_token, uintptr_t out, int64_t ldx, int64_t ldo, int S,
+           int T, int H, int dt, uintptr_t stream) {
+          MoeGatherArgs a;
+          a.x = (const void*)x; a.row_token = (const int*)row_token; a.out = (void*)out;
+          a.ldx = ldx; a.ldo = ldo;
+          a.S = S; a.T = T; a.H = H;
+          check(moe_gather_launch(a, dt, (hipStream_t)stream), "moe_gather");
+        },
+        py::arg("x"), py::arg("row_token"), py::arg("out"), py::arg("ldx"), py::arg("ldo"),
+        py::arg("S"), py::arg("T"), py::arg("H"), py::arg("dt"), py::arg("stream") = 0);
+  m.def("moe_combine_bwd",
+        [](uintptr_t dout, uintptr_t slot_row, uintptr_t gate, uintptr_t row_token, uintptr_t y,
+           uintptr_t dy, uintptr_t dgate, int64_t lddo, int64_t ldy, int64_t lddy, int S, int k,
+           int T, int H, int din, int dout_dt, uintptr_t stream) {
+          MoeCombineBwdArgs a;
+          a.dout = (const void*)dout; a.slot_row = (const int*)slot_row;
+          a.gate = (const float*)gate; a.row_token = (const int*)row_token;
+          a.y = (const void*)y; a.dy = (void*)dy; a.dgate = (float*)dgate;
+          a.lddo = lddo; a.ldy = ldy; a.lddy = lddy;
+          a.S = S; a.k = k; a.T = T; a.H = H;
+          check(moe_combine_bwd_launch(a, din, dout_dt, (hipStream_t)stream), "moe_combine_bwd");
+        },
+        py::arg("dout"), py::arg("slot_row"), py::arg("gate"), py::arg("row_token"),
+        py::arg("y"), py::arg("dy"), py::arg("dgate"), py::arg("lddo"), py::arg("ldy"),
+        py::arg("lddy"), py::arg("S"), py::arg("k"), py::arg("T"), py::arg("H"), py::arg("din"),
+        py::arg("dout_dt"), py::arg("stream") = 0);
+  m.def("glu_fwd",
+        [](uintptr_t c, uintptr_t out, int64_t ldc, int64_t ldo, int T, int F, int act, int din,
+           int dout, uintptr_t stream) {
+          GluArgs a;
+          a.c = (const void*)c; a.out = (void*)out;
+          a.ldc = ldc; a.ldo = ldo;
+          a.T = T; a.F = F; a.act = act;
+          check(glu_fwd_launch(a, din, dout, (hipStream_t)stream), "glu_fwd");
+        },
+        py::arg("c"), py::arg("out"), py::arg("ldc"), py::arg("ldo"), py::arg("T"), py::arg("F"),
+        py::arg("act"), py::arg("din"), py::arg("dout"), py::arg("stream") = 0);
+  m.def("glu_bwd",
+        [](uintptr_t dh, uintptr_t c, uintptr_t out, int64_t ldh, int64_t ldc, int64_t ldo, int T,
+           int F, int act, int din, uintptr_t stream) {
+          GluArgs a;
+          a.dh = (const void*)dh; a.c = (const void*)c; a.out = (void*)out;
+          a.ldh = ldh; a.ldc = ldc; a.ldo = ldo;
+          a.T = T; a.F = F; a.act = act;
+          check(glu_bwd_launch(a, din, (hipStream_t)stream), "glu_bwd");
+        },
+        py::arg("dh"), py::arg("c"), py::arg("out"), py::arg("ldh"), py::arg("ldc"),
+        py::arg("ldo"), py::arg("T"), py::arg("F"), py::arg("act"), py::arg("din"),
+        py::arg("stream") = 0);
   m.def("mx_quantize_t",  // x[R, C] -> qt[C, R] (fp4: [C, R / 2]) + st[C, R / 32], blocks down
         // the columns of x; two: also the row-wise q[R, C] (fp4: [R, C / 2]) + s[R, C / 32]
         [](uintptr_t x, uintptr_t qt, uintptr_t st, int64_t ldx, int64_t ldqt, int64_t ldst,

@@ -14,44 +14,11 @@
 
 #include "gemm/gemm.h"
 #include "gemm/mx_quant_in.h"
+#include "gemm/row_io.h"
 #include "moe.h"
 
 namespace ddlb {
 namespace {
-
-constexpr int kCombineThreads = 256;
-constexpr int kCombineK = 8;
-
-__device__ __forceinline__ unsigned combine_bf16_rne(float f) {
-  const unsigned u = __builtin_bit_cast(unsigned, f);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0u;  // NaN
-  return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-
-// N f32 values -> the output dtype, one RNE rounding each, stored as 16-byte vectors (N = 4
-// into f32 or N = 8 into 16 bits: one; N = 8 into f32: two)
-template <int OUT, int N>
-__device__ __forceinline__ void combine_store(char* p, const float* acc) {
-  if constexpr (OUT == DT_F32) {
-#pragma unroll
-    for (int i = 0; i < N; i += 4)
-      *(float4*)(p + 4 * i) = float4{acc[i], acc[i + 1], acc[i + 2], acc[i + 3]};
-  } else {
-    static_assert(N == 8, "16-bit outputs come from 16-bit inputs");
-    unsigned w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if constexpr (OUT == DT_BF16) {
-        w[i] = combine_bf16_rne(acc[2 * i]) | (combine_bf16_rne(acc[2 * i + 1]) << 16);
-      } else {
-        const _Float16 lo = (_Float16)acc[2 * i], hi = (_Float16)acc[2 * i + 1];
-        w[i] = (unsigned)__builtin_bit_cast(unsigned short, lo) |
-               ((unsigned)__builtin_bit_cast(unsigned short, hi) << 16);
-      }
-    }
-    *(mxq_u32x4*)p = mxq_u32x4{w[0], w[1], w[2], w[3]};
-  }
-}
 
 template <int DT, int N>
 __device__ __forceinline__ void combine_add(float* acc, const MoeCombineArgs& a, int row, float g,
@@ -76,17 +43,13 @@ __device__ __forceinline__ void combine_add(float* acc, const MoeCombineArgs& a,
 }
 
 template <int DT, int OUT, bool REGS>
-__global__ __launch_bounds__(kCombineThreads) void moe_combine_kernel(const MoeCombineArgs a,
+__global__ __launch_bounds__(kRowThreads) void moe_combine_kernel(const MoeCombineArgs a,
                                                                       int rows_pp) {
   constexpr int N = MxqIn<DT>::kElems;  // elements per 16-byte vector of y
   constexpr int OSZ = OUT == DT_F32 ? 4 : 2;
   const int vpr = a.H / N;              // vectors per row
-  const int tid = threadIdx.x;
-  int r_in = 0, c0 = tid;
-  if (vpr < kCombineThreads) {
-    r_in = tid / vpr;
-    c0 = tid - r_in * vpr;
-  }
+  int r_in, c0;
+  row_lane(vpr, threadIdx.x, r_in, c0);
   if (r_in >= rows_pp) return;
   const int64_t step = (int64_t)gridDim.x * rows_pp;
   for (int64_t t = (int64_t)blockIdx.x * rows_pp + r_in; t < a.S; t += step) {
@@ -102,7 +65,7 @@ __global__ __launch_bounds__(kCombineThreads) void moe_combine_kernel(const MoeC
         g[j] = j < a.k ? gates[j] : 0.0f;
       }
     }
-    for (int c = c0; c < vpr; c += kCombineThreads) {
+    for (int c = c0; c < vpr; c += kRowThreads) {
       float acc[N];
 #pragma unroll
       for (int i = 0; i < N; ++i) acc[i] = 0.0f;
@@ -112,36 +75,19 @@ __global__ __launch_bounds__(kCombineThreads) void moe_combine_kernel(const MoeC
       } else {
         for (int j = 0; j < a.k; ++j) combine_add<DT, N>(acc, a, rows[j], gates[j], c);
       }
-      combine_store<OUT, N>(orow + (int64_t)c * N * OSZ, acc);
+      row_store<OUT, N>(orow + (int64_t)c * N * OSZ, acc);
     }
   }
 }
 
-int combine_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        n <= 0)
-      n = 256;
-  }
-  return n;
-}
-
 template <int DT, int OUT>
 hipError_t combine_go(const MoeCombineArgs& a, hipStream_t s) {
-  const int vpr = a.H / MxqIn<DT>::kElems;
-  const int rows_pp = vpr < kCombineThreads ? kCombineThreads / vpr : 1;
-  int64_t grid = ((int64_t)a.S + rows_pp - 1) / rows_pp;
-  const int64_t cap = (int64_t)combine_cus() * 8;
-  if (grid > cap) grid = cap;
+  const int rows_pp = rows_per_pass(a.H / MxqIn<DT>::kElems);
+  const dim3 grid(row_grid(a.S, rows_pp)), block(kRowThreads);
   if (a.k <= kCombineK)
-    hipLaunchKernelGGL((moe_combine_kernel<DT, OUT, true>), dim3((unsigned)grid),
-                       dim3(kCombineThreads), 0, s, a, rows_pp);
+    hipLaunchKernelGGL((moe_combine_kernel<DT, OUT, true>), grid, block, 0, s, a, rows_pp);
   else
-    hipLaunchKernelGGL((moe_combine_kernel<DT, OUT, false>), dim3((unsigned)grid),
-                       dim3(kCombineThreads), 0, s, a, rows_pp);
+    hipLaunchKernelGGL((moe_combine_kernel<DT, OUT, false>), grid, block, 0, s, a, rows_pp);
   return hipGetLastError();
 }
 

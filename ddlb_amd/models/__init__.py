@@ -7,6 +7,8 @@
   fc1 writes its activation quantised from the GEMM epilogue, fc2 reads it.
 * :mod:`ddlb_amd.models.mx_moe`  — one-GPU routed (mixture-of-experts) gated FFN: tokens sorted by
   expert on the device, one grouped GEMM launch per layer (``ops.gemm.gemm_grouped``).
+* :mod:`ddlb_amd.models.mx_moe_ffn` — the trainable routed gated FFN: autograd through the
+  dispatch, the GLU and the combine around two ``mx_grouped_linear`` layers.
 * :mod:`ddlb_amd.models.mx_linear` — a trainable one-GPU MX linear layer: forward, dgrad and
   wgrad on the block-scaled GEMMs, operands quantised along each GEMM's own contraction axis.
 """

@@ -12,8 +12,9 @@ owns rows ``[o'[g], o'[g + 1])`` with the offsets clamped as ``ops.gemm.clamp_of
 Forward and dgrad are ``ops.gemm.gemm_grouped``; the wgrad is ``ops.gemm.gemm_kgrouped`` on the
 padded K layout that ``ops.mx.quantize_mx_t_grouped`` writes for ``X`` and ``dY`` (each group's
 blocks start at the group's first row, its tail is zero-padded to a whole K-tile). ``Wtq`` is the
-stacked form of the same quantiser: one launch for all experts. Nothing waits for the device, so
-the whole step can be captured in a graph. Saved for backward: the grouped-transposed ``X`` and
+stacked form of the same quantiser: one launch for all experts. Nothing waits for the device
+(a graph capture that holds autograd's backward is another matter: see
+``ddlb_amd.models.mx_moe_ffn.refuse_captured_backward``). Saved for backward: the grouped-transposed ``X`` and
 ``Wtq`` (1 or 0.5 byte per element plus scales), not the 16-bit tensors.
 
 ``T`` is free; ``K`` and ``N`` are multiples of 128 (MXFP4: 256), being the contraction lengths of

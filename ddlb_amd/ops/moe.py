@@ -8,8 +8,14 @@ gate weights through the inverted index ``slot_row`` in a fixed order
 :func:`ddlb_amd.ops.mx.quantize_mx_gather` quantises ``x[row_token]`` without writing the
 permuted copy and ``ops.gemm.gemm_grouped`` runs the experts.
 
-:func:`route_reference` and :func:`combine_reference` are pure torch, run on any device and are the
-specification; on the GPU the kernels agree with them bit for bit.
+For training (``ddlb_amd.models.mx_moe_ffn``): ``gather`` writes the permuted 16-bit copy
+``x[row_token]`` (``csrc/moe/moe_gather.hip``; its backward is ``combine`` with gates of 1) and
+``combine_bwd`` is the backward of ``combine`` (``csrc/moe/moe_combine_bwd.hip``): the rows'
+gradient and, reduced in a fixed order without atomics, the gate weights'.
+
+:func:`route_reference`, :func:`combine_reference`, :func:`gather_reference` and
+:func:`combine_bwd_reference` are pure torch, run on any device and are the specification; on the
+GPU the kernels agree with them bit for bit (``dgate``: to fp32 summation accuracy).
 """
 
 from __future__ import annotations
@@ -246,3 +252,264 @@ def combine_reference(y, slot_row, gate, out_dtype=None):
         prod = gate[:, j:j + 1] * rows
         acc = torch.where(valid.unsqueeze(1), acc + prod, acc)
     return acc.to(out_dtype or y.dtype)
+
+
+def _check_rows(what, name, t, rows, cols):
+    """``t [rows, cols]`` row-major with unit inner stride and 16-byte-aligned rows of whole
+    16-byte vectors (:func:`combine`'s layout rules)."""
+    if tuple(t.shape) != (rows, cols):
+        raise ValueError(f"{name} must have shape {(rows, cols)}, not {tuple(t.shape)}")
+    if (cols * t.element_size()) % 16:
+        raise ValueError(f"{what} needs rows of whole 16-byte vectors ({name} is {rows} x {cols} "
+                         f"{t.dtype})")
+    if rows == 0 or cols == 0:
+        return
+    if t.stride(1) != 1 or (rows > 1 and t.stride(0) < cols):
+        raise ValueError(f"{what} needs row-major {name} with unit inner stride")
+    if t.data_ptr() % 16 or (rows > 1 and (t.stride(0) * t.element_size()) % 16):
+        raise ValueError(f"{what} needs 16-byte-aligned rows of {name}")
+
+
+def _ld(t):
+    return max(t.stride(0), t.shape[1]) if t.shape[0] > 1 else t.shape[1]
+
+
+def _check_index(name, t, like, shape=None):
+    import torch
+
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+        raise TypeError(f"{name} must be an int32 tensor, not {getattr(t, 'dtype', type(t))}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)}, not {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous (strides {tuple(t.stride())})")
+    if t.device != like.device:
+        raise ValueError(f"{name} is on {t.device}, the rows on {like.device}")
+
+
+def _check_gather(x, row_token, out=None):
+    """Every refusal of :func:`gather`, on the host and before the extension is loaded (CPU
+    tensors reach the device refusal). Returns ``(S, T, H)``."""
+    import torch
+
+    dts = (torch.bfloat16, torch.float16, torch.float32)
+    if not isinstance(x, torch.Tensor) or x.dtype not in dts:
+        raise TypeError(f"x must be one of {Y_DTYPES}, not {getattr(x, 'dtype', type(x))}")
+    if x.dim() != 2:
+        raise ValueError(f"x must be [S, H] (2-D), not {tuple(x.shape)}")
+    _check_index("row_token", row_token, x)
+    if row_token.dim() != 1:
+        raise ValueError(f"row_token must be [T] (1-D), not {tuple(row_token.shape)}")
+    S, H = x.shape
+    T = row_token.shape[0]
+    if S >= 2 ** 31 or H >= 2 ** 31 or T >= 2 ** 31:
+        raise ValueError("dimensions must fit in 32 bits")
+    _check_rows("gather", "x", x, S, H)
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != x.dtype:
+            raise TypeError(f"out must be a tensor of x's dtype {x.dtype}, not "
+                            f"{getattr(out, 'dtype', type(out))}")
+        if out.device != x.device:
+            raise ValueError(f"out is on {out.device}, x on {x.device}")
+        _check_rows("gather", "out", out, T, H)
+    if x.device.type != "cuda":  # last, so that CPU tensors reach every refusal above
+        raise ValueError("gather needs ROCm device tensors (gather_reference runs anywhere)")
+    return S, T, H
+
+
+def gather(x, row_token, *, out=None, stream=None):
+    """The HIP dense gather of the routed rows (``csrc/moe/moe_gather.hip``):
+    ``xp[r, :] = x[row_token[r], :]`` with ``x [S, H]`` bf16 / f16 / f32 and ``row_token [T]``
+    int32 (:func:`route`); a row whose index is outside ``[0, S)`` is ``+0.0`` and nothing is read
+    for it. Byte for byte ``index_select`` with zero rows (:func:`gather_reference`). The layout
+    and alignment rules are :func:`combine`'s; :func:`_check_gather` holds every refusal.
+
+    The training path's permuted copy: ``mx_grouped_linear`` quantises the 16-bit rows twice. The
+    inference path (:func:`ddlb_amd.ops.mx.quantize_mx_gather`) writes no such copy. Its backward
+    is :func:`combine` with gates of 1."""
+    import torch
+
+    from ddlb_amd.ops import load
+    from ddlb_amd.ops.gemm import dtype_code
+
+    S, T, H = _check_gather(x, row_token, out)
+    if out is None:
+        out = torch.empty((T, H), dtype=x.dtype, device=x.device)
+    C = load()
+    if T == 0 or H == 0:
+        return out
+    strm = stream if stream is not None else torch.cuda.current_stream(x.device).cuda_stream
+    with torch.cuda.device(x.device):
+        C.moe_gather(x=x.data_ptr(), row_token=row_token.data_ptr(), out=out.data_ptr(),
+                     ldx=_ld(x), ldo=_ld(out), S=S, T=T, H=H, dt=dtype_code(x.dtype),
+                     stream=strm)
+    if stream is not None:  # the output stays allocated until that stream reaches it
+        out.record_stream(torch.cuda.ExternalStream(strm))
+    return out
+
+
+def gather_reference(x, row_token):
+    """The specification of :func:`gather` in torch ops, on any device."""
+    import torch
+
+    S, H = x.shape
+    r = row_token.to(torch.int64)
+    valid = (r >= 0) & (r < S)
+    out = torch.zeros((r.shape[0], H), dtype=x.dtype, device=x.device)
+    if S:
+        rows = x.index_select(0, torch.where(valid, r, torch.zeros_like(r)))
+        out = torch.where(valid.unsqueeze(1), rows, out)
+    return out
+
+
+def _check_combine_bwd(dout, slot_row, gate, row_token, y=None, dy_dtype=None, out=None):
+    """Every refusal of :func:`combine_bwd`, on the host and before the extension is loaded (CPU
+    tensors reach the device refusal). Returns ``(S, k, T, H, dy's dtype)``."""
+    import torch
+
+    dts = (torch.bfloat16, torch.float16, torch.float32)
+    if not isinstance(dout, torch.Tensor) or dout.dtype not in dts:
+        raise TypeError(f"dout must be one of {Y_DTYPES}, not "
+                        f"{getattr(dout, 'dtype', type(dout))}")
+    if dout.dim() != 2:
+        raise ValueError(f"dout must be [S, H] (2-D), not {tuple(dout.shape)}")
+    S, H = dout.shape
+    _check_index("slot_row", slot_row, dout)
+    if slot_row.dim() != 2 or slot_row.shape[1] < 1 or slot_row.shape[0] != S:
+        raise ValueError(f"slot_row must be [S, k] with S = {S} and k >= 1, not "
+                         f"{tuple(slot_row.shape)}")
+    k = slot_row.shape[1]
+    if not isinstance(gate, torch.Tensor) or gate.dtype != torch.float32:
+        raise TypeError(f"gate must be a float32 tensor, not "
+                        f"{getattr(gate, 'dtype', type(gate))}")
+    if tuple(gate.shape) != (S, k):
+        raise ValueError(f"gate must have slot_row's shape {(S, k)}, not {tuple(gate.shape)}")
+    if not gate.is_contiguous():
+        raise ValueError("slot_row and gate must be contiguous")
+    if gate.device != dout.device:
+        raise ValueError(f"gate is on {gate.device}, dout on {dout.device}")
+    _check_index("row_token", row_token, dout)
+    if row_token.dim() != 1:
+        raise ValueError(f"row_token must be [T] (1-D), not {tuple(row_token.shape)}")
+    T = row_token.shape[0]
+    if T >= 2 ** 31 or H >= 2 ** 31 or S * k >= 2 ** 31:
+        raise ValueError("dimensions must fit in 32 bits")
+    if y is not None and (not isinstance(y, torch.Tensor) or y.dtype not in dts):
+        raise TypeError(f"y must be one of {Y_DTYPES}, not {getattr(y, 'dtype', type(y))}")
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise TypeError("out must be a pair (dy, dgate); dgate is None without y")
+        if not isinstance(out[0], torch.Tensor) or out[0].dtype not in dts:
+            raise TypeError(f"out[0] (dy) must be one of {Y_DTYPES}, not "
+                            f"{getattr(out[0], 'dtype', type(out[0]))}")
+    given = [t.dtype for t in (y, out[0] if out is not None else None) if t is not None]
+    if dy_dtype is not None:
+        given.append(dy_dtype)
+    ddt = given[0] if given else dout.dtype
+    if any(d != ddt for d in given):
+        raise TypeError(f"y, out[0] and dy_dtype must agree on dy's dtype, not {given}")
+    if ddt not in dts or (ddt != dout.dtype and dout.dtype != torch.float32):
+        raise TypeError(f"combine_bwd of a {dout.dtype} dout writes {dout.dtype} rows (a float32 "
+                        f"dout: any of {Y_DTYPES}), not {ddt}")
+    _check_rows("combine_bwd", "dout", dout, S, H)
+    if (H * torch.empty((), dtype=ddt).element_size()) % 16:
+        raise ValueError(f"combine_bwd needs rows of whole 16-byte vectors (dy is {T} x {H} "
+                         f"{ddt})")
+    if y is not None:
+        if y.device != dout.device:
+            raise ValueError(f"y is on {y.device}, dout on {dout.device}")
+        _check_rows("combine_bwd", "y", y, T, H)
+    if out is not None:
+        dy, dgate = out
+        if dy.device != dout.device:
+            raise ValueError(f"out[0] (dy) is on {dy.device}, dout on {dout.device}")
+        _check_rows("combine_bwd", "out[0] (dy)", dy, T, H)
+        if (dgate is None) != (y is None):
+            raise ValueError("out[1] (dgate) goes with y: both or neither")
+        if dgate is not None:
+            if not isinstance(dgate, torch.Tensor) or dgate.dtype != torch.float32:
+                raise TypeError(f"out[1] (dgate) must be a float32 tensor, not "
+                                f"{getattr(dgate, 'dtype', type(dgate))}")
+            if tuple(dgate.shape) != (S, k) or not dgate.is_contiguous():
+                raise ValueError(f"out[1] (dgate) must be contiguous with shape {(S, k)}, not "
+                                 f"{tuple(dgate.shape)}")
+            if dgate.device != dout.device:
+                raise ValueError(f"out[1] (dgate) is on {dgate.device}, dout on {dout.device}")
+    if dout.device.type != "cuda":  # last, so that CPU tensors reach every refusal above
+        raise ValueError("combine_bwd needs ROCm device tensors (combine_bwd_reference runs "
+                         "anywhere)")
+    return S, k, T, H, ddt
+
+
+def combine_bwd(dout, slot_row, gate, row_token, y=None, *, dy_dtype=None, out=None,
+                stream=None):
+    """The backward of :func:`combine` (``csrc/moe/moe_combine_bwd.hip``): ``dout [S, H]`` bf16 /
+    f16 / f32 -> ``(dy [T, H], dgate [S, k] | None)``. ``dy`` has ``dy_dtype``: ``dout``'s dtype
+    (default) or, for a float32 ``dout``, any of the three (the mirror of :func:`combine`'s
+    pairs); ``y [T, H]``, the forward's input, has ``dy``'s dtype.
+
+    Precondition: ``(row_token, slot_row)`` are mutually inverse, as :func:`route` writes them.
+    Then every element of ``dy`` and ``dgate`` is written: for ``t = row_token[r]`` in ``[0, S)``
+    and the ``j`` with ``slot_row[t, j] == r``, ``dy[r, c] = rne(gate[t, j] * float(dout[t, c]))``,
+    one fp32 multiply and one rounding, bit for bit ``(gate[t, j] * dout[t].float()).to(dtype)``;
+    the other rows (the padding behind ``offsets[E]``) are ``+0.0``. ``dgate[t, j]`` is the fp32
+    sum over ``c`` of ``float(dout[t, c]) * float(y[slot_row[t, j], c])`` in a fixed order (bitwise
+    reproducible, no atomics) and ``+0.0`` for a dropped or out-of-range slot, whose row is not
+    read; it is what trains a router. ``y=None``: the gates need no gradient, the dot products are
+    skipped and ``dgate`` is ``None``. Without the precondition every index is still
+    range-checked before use; the values are then unspecified. :func:`_check_combine_bwd` holds
+    every refusal."""
+    import torch
+
+    from ddlb_amd.ops import load
+    from ddlb_amd.ops.gemm import dtype_code
+
+    S, k, T, H, ddt = _check_combine_bwd(dout, slot_row, gate, row_token, y, dy_dtype, out)
+    dev = dout.device
+    if out is None:
+        dy = torch.empty((T, H), dtype=ddt, device=dev)
+        dgate = None if y is None else torch.empty((S, k), dtype=torch.float32, device=dev)
+    else:
+        dy, dgate = out
+    C = load()
+    if dgate is not None and (T == 0 or H == 0):
+        dgate.zero_()  # no row to read
+    if H == 0 or T == 0:
+        return dy, dgate
+    strm = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        C.moe_combine_bwd(dout=dout.data_ptr(), slot_row=slot_row.data_ptr(),
+                          gate=gate.data_ptr(), row_token=row_token.data_ptr(),
+                          y=0 if y is None else y.data_ptr(), dy=dy.data_ptr(),
+                          dgate=0 if dgate is None else dgate.data_ptr(), lddo=_ld(dout),
+                          ldy=H if y is None else _ld(y), lddy=_ld(dy), S=S, k=k, T=T, H=H,
+                          din=dtype_code(dout.dtype), dout_dt=dtype_code(ddt), stream=strm)
+    if stream is not None:  # the outputs stay allocated until that stream reaches them
+        for t in (dy, dgate):
+            if t is not None:
+                t.record_stream(torch.cuda.ExternalStream(strm))
+    return dy, dgate
+
+
+def combine_bwd_reference(dout, slot_row, gate, row_token, y=None, dy_dtype=None):
+    """The specification of :func:`combine_bwd` in torch ops, on any device: ``dy`` with the same
+    fp32 multiply and one rounding, ``dgate`` in fp64 (``None`` without ``y``)."""
+    import torch
+
+    S, k = slot_row.shape
+    T = row_token.shape[0]
+    H = dout.shape[1]
+    ddt = dy_dtype or (y.dtype if y is not None else dout.dtype)
+    dy = torch.zeros((T, H), dtype=ddt, device=dout.device)
+    dgate = None if y is None else torch.zeros((S, k), dtype=torch.float64, device=dout.device)
+    if T == 0 or S == 0:
+        return dy, dgate
+    d32 = dout.to(torch.float32)
+    for j in range(k):
+        r = slot_row[:, j].to(torch.int64)
+        valid = ((r >= 0) & (r < T)).nonzero().flatten()
+        rows = r[valid]
+        dy[rows] = (gate[valid, j:j + 1] * d32[valid]).to(ddt)
+        if y is not None:
+            dgate[valid, j] = (d32[valid].double() * y[rows].double()).sum(dim=1)
+    return dy, dgate
