@@ -312,7 +312,7 @@ struct MxQuantTArgs {
 hipError_t mx_quantize_t_launch(const MxQuantTArgs& a, int din, bool fp4, bool two,
                                 hipStream_t s);
 
-// Grouped transposing MX quantiser (csrc/gemm/mx_quant_t_grouped.hip): x[T, C], the rows sorted
+// Grouped transposing MX quantiser (csrc/gemm/mx_quant_t.hip, the grouped form): x[T, C], sorted
 // into ngroups groups by the DEVICE array offs (ngroups + 1 int32, clamped to T as a grouped GEMM
 // clamps them, read by the kernel only) -> qt[C, cap] (fp4: [C, cap / 2]) and st[C, cap / 32],
 // cap = kgrouped_capacity(T, ngroups, MOD), MOD = 128 (fp4: 256): columns [k0_g, k0_g + kl_g) of

@@ -1,15 +1,9 @@
-// The grouped form of the tiled kernel (GemmArgs::grp_offs) and its launch template, included by
-// the gemm_grouped_*.hip translation units only.
+// The M-grouped form of the tiled kernel (GemmArgs::grp_offs): its prologue and its launch
+// template, included by the gemm_grouped_*.hip translation units only.
 //
-// gemm_tn_grouped_kernel runs the body of gemm_tn_kernel (gemm_kernels.h), the SAME TEXT, on one
-// tile of one group. gemm_kernels.h is not edited for it: the build (ddlb_amd/_build.py,
-// grouped_body()) copies the body of gemm_tn_kernel, from the line behind its signature to its
-// closing brace, into gemm_tn_grouped_body.gen.h and replaces exactly one line of it, the choice
-// of the tile (`const int wg = tile_index(p, nwg);` becomes `const int wg = wg_group;`); a body
-// that no longer holds that line exactly once fails the build. That file is included below,
-// between this kernel's prologue and its closing brace. So the ungrouped instantiations are
-// compiled from the text they always were, with no run-time branch and no template argument
-// added, and their registers are the parent's (docs/ARCHITECTURE.md "Grouped GEMM").
+// The kernel is gemm_tn_kernel itself (gemm_kernels.h) with GRP = TILE_GROUPED_M: grouped_args
+// below runs in front of its body, which then works on one tile of one group. The ungrouped
+// instantiations do not see it (docs/ARCHITECTURE.md "One kernel template, three prologues").
 #pragma once
 #include "gemm_kernels.h"
 
@@ -49,17 +43,7 @@ __device__ __forceinline__ bool grouped_args(const GemmArgs& pl, GemmArgs& pg, i
   return true;
 }
 
-template <class Mma, int OUT, int BM, int BN, int WM, int WN, bool GLU = false>
-__global__ __launch_bounds__(WM* WN * 64) void gemm_tn_grouped_kernel(const GemmArgs p_launch) {
-  constexpr bool ILV = false;  // the codes of mxs_offers(): never interleaved
-  GemmArgs p_group;
-  int wg_group;
-  if (!grouped_args<Mma, OUT, BM, BN>(p_launch, p_group, wg_group)) return;
-  const GemmArgs& p = p_group;
-#include "gemm_tn_grouped_body.gen.h"
-}
-
-// launch_tiled's sibling for the grouped kernel, its one launch site (gated or not): the codes of
+// launch_tiled's sibling for the M-grouped form, its one launch site (gated or not): the codes of
 // mxs_offers() (NR = 4, no DMA interleave), anything else hipErrorInvalidValue; the byte view of
 // fp4 operands / an fp4 output is formed here as launch_tiled forms it; the grid is the bound of
 // tile_map.h, which gemm_launch has checked to be a grid.
@@ -78,11 +62,11 @@ hipError_t launch_tiled_grouped(const GemmArgs& p_in, int tile, hipStream_t s) {
                                                    (p.N + c.cols - 1) / c.cols));
       const dim3 block(c.wm * c.wn * 64);
       if (p.glu)
-        hipLaunchKernelGGL((gemm_tn_grouped_kernel<Mma, OUT, c.rows, c.cols, c.wm, c.wn, true>),
-                           grid, block, 0, s, p);
+        hipLaunchKernelGGL((gemm_tn_kernel<Mma, OUT, c.rows, c.cols, c.wm, c.wn, false, true,
+                                           TILE_GROUPED_M>), grid, block, 0, s, p);
       else
-        hipLaunchKernelGGL((gemm_tn_grouped_kernel<Mma, OUT, c.rows, c.cols, c.wm, c.wn>), grid,
-                           block, 0, s, p);
+        hipLaunchKernelGGL((gemm_tn_kernel<Mma, OUT, c.rows, c.cols, c.wm, c.wn, false, false,
+                                           TILE_GROUPED_M>), grid, block, 0, s, p);
       return hipGetLastError();
     }
   });

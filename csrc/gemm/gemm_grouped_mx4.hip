@@ -1,5 +1,5 @@
 // gemm_grouped_mx4: the grouped form of the tiled kernel (GemmArgs::grp_offs;
-// gemm_tn_grouped_kernel, gemm_grouped_kernels.h), ungated and gated, the four codes of
+// gemm_tn_kernel<.., TILE_GROUPED_M>, gemm_grouped_kernels.h), ungated and gated, the four codes of
 // mxs_offers(): block-scaled fp4 operands, bf16 / f16 / f32 out.
 #include "gemm_grouped_kernels.h"
 #include "gemm_entry.h"

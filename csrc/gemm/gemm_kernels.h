@@ -9,6 +9,7 @@
 
 #include <type_traits>
 
+#include "device_info.h"
 #include "gemm.h"
 #include "mx_cvt.h"
 #include "tile_map.h"
@@ -400,8 +401,32 @@ __device__ __forceinline__ void wait_tile(const GemmArgs& p, int64_t m0, int BM)
 // Any shape on the fast path (ragged edges: clamped row loads, guarded stores). With MmaMX the
 // compute step is one v_mfma_scale_f32_16x16x128_f8f6f4 per 128-byte K-row (unit E8M0 scales =
 // 127): 2x the bf16 MFMA rate (MI355X_MICROARCH.md "Matrix cores"), same staging.
-template <class Mma, int OUT, int BM, int BN, int WM, int WN, bool ILV = false, bool GLU = false>
-__global__ __launch_bounds__(WM* WN * 64) void gemm_tn_kernel(const GemmArgs p) {
+//
+// GRP chooses what runs in front of the body, at compile time. TILE_PLAIN (the default): nothing;
+// p is the kernel argument and the workgroup's tile comes from tile_index. TILE_GROUPED_M /
+// TILE_GROUPED_K (GemmArgs::grp_offs; the launch templates of gemm_grouped_kernels.h /
+// gemm_kgrouped_kernels.h, where the two prologues are defined): the prologue re-bases a copy of
+// the arguments to the workgroup's group and names its tile within the group, or finds no work
+// and returns before any barrier or LDS-DMA. The body is the same text for all three.
+enum TileGrouping { TILE_PLAIN = 0, TILE_GROUPED_M = 1, TILE_GROUPED_K = 2 };
+template <class Mma, int OUT, int BM, int BN>
+__device__ __forceinline__ bool grouped_args(const GemmArgs& pl, GemmArgs& pg, int& wg);
+template <class Mma, int OUT, int BM, int BN, int NT>
+__device__ __forceinline__ bool kgrouped_args(const GemmArgs& pl, GemmArgs& pg, int& wg);
+
+template <class Mma, int OUT, int BM, int BN, int WM, int WN, bool ILV = false, bool GLU = false,
+          int GRP = TILE_PLAIN>
+__global__ __launch_bounds__(WM* WN * 64) void gemm_tn_kernel(const GemmArgs p_launch) {
+  static_assert(GRP == TILE_PLAIN || !ILV, "grouped: the codes of mxs_offers(), never interleaved");
+  static_assert(GRP != TILE_GROUPED_K || !GLU, "K-grouped: ungated");
+  [[maybe_unused]] GemmArgs p_group;
+  [[maybe_unused]] int wg_group;
+  if constexpr (GRP == TILE_GROUPED_M) {
+    if (!grouped_args<Mma, OUT, BM, BN>(p_launch, p_group, wg_group)) return;
+  } else if constexpr (GRP == TILE_GROUPED_K) {
+    if (!kgrouped_args<Mma, OUT, BM, BN, WM * WN * 64>(p_launch, p_group, wg_group)) return;
+  }
+  const GemmArgs& p = GRP == TILE_PLAIN ? p_launch : p_group;  // (plain: the argument itself)
   constexpr int NT = WM * WN * 64, NW = WM * WN;
   constexpr int ROWB = 128;  // bytes per row per K-tile
   constexpr int A_BYTES = BM * ROWB, B_BYTES = BN * ROWB, STAGE = A_BYTES + B_BYTES;
@@ -413,7 +438,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_tn_kernel(const GemmArgs p) 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int tiles_n = (p.N + BN - 1) / BN, tiles_m = (p.M + BM - 1) / BM;
   const int nwg = tiles_m * tiles_n;
-  const int wg = tile_index(p, nwg);
+  const int wg = GRP == TILE_PLAIN ? tile_index(p, nwg) : wg_group;
   const int tm = wg / tiles_n, tn = wg % tiles_n;
   const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
 
@@ -2186,17 +2211,6 @@ hipError_t launch_tiled(const GemmArgs& p_in, int tile, hipStream_t s) {
   };
   if constexpr (in4 || out4) return launch(fp4_byte_view(p_in, in4, out4));
   else return launch(p_in);
-}
-
-int num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-  }
-  return n;
 }
 
 // t8 takes whole 256x256 tiles (flags, grouped rows, shard tables and activations allowed)

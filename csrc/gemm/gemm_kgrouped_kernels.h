@@ -1,12 +1,11 @@
-// The K-grouped form of the tiled kernel (GemmArgs::kgrouped) and its launch template, included
-// by the gemm_kgrouped_*.hip translation units only.
+// The K-grouped form of the tiled kernel (GemmArgs::kgrouped): its prologue and its launch
+// template, included by the gemm_kgrouped_*.hip translation units only.
 //
-// gemm_tn_kgrouped_kernel is a second prologue in front of the generated body that
-// gemm_tn_grouped_kernel includes (gemm_tn_grouped_body.gen.h: the body of gemm_tn_kernel with its
-// tile choice replaced, ddlb_amd/_build.py). Where the M-grouped prologue re-bases the ROWS of a
-// and c to a group, this one re-bases the COLUMNS of both operands and of both scale arrays to
-// the group's range of the padded contraction axis (tile_map.h kgrouped_range) and the output to
-// the group's own [M, N] matrix. gemm_kernels.h is not edited for it.
+// The kernel is gemm_tn_kernel itself (gemm_kernels.h) with GRP = TILE_GROUPED_K: kgrouped_args
+// below runs in front of its body. Where the M-grouped prologue (gemm_grouped_kernels.h) re-bases
+// the ROWS of a and c to a group, this one re-bases the COLUMNS of both operands and of both scale
+// arrays to the group's range of the padded contraction axis (tile_map.h kgrouped_range) and the
+// output to the group's own [M, N] matrix.
 #pragma once
 #include "gemm_kernels.h"
 
@@ -52,17 +51,7 @@ __device__ __forceinline__ bool kgrouped_args(const GemmArgs& pl, GemmArgs& pg, 
   return true;
 }
 
-template <class Mma, int OUT, int BM, int BN, int WM, int WN>
-__global__ __launch_bounds__(WM* WN * 64) void gemm_tn_kgrouped_kernel(const GemmArgs p_launch) {
-  constexpr bool ILV = false, GLU = false;  // the codes of mxs_offers(), ungated
-  GemmArgs p_group;
-  int wg_group;
-  if (!kgrouped_args<Mma, OUT, BM, BN, WM * WN * 64>(p_launch, p_group, wg_group)) return;
-  const GemmArgs& p = p_group;
-#include "gemm_tn_grouped_body.gen.h"
-}
-
-// launch_tiled_grouped's sibling, the one launch site of the K-grouped kernel: the codes of
+// launch_tiled_grouped's sibling, the one launch site of the K-grouped form: the codes of
 // mxs_offers(), anything else hipErrorInvalidValue; gemm_launch has checked that the grid is one.
 template <class Mma, int OUT>
 hipError_t launch_tiled_kgrouped(const GemmArgs& p_in, int tile, hipStream_t s) {
@@ -77,8 +66,8 @@ hipError_t launch_tiled_kgrouped(const GemmArgs& p_in, int tile, hipStream_t s) 
       const int64_t tiles = (int64_t)((p.M + c.rows - 1) / c.rows) * ((p.N + c.cols - 1) / c.cols);
       const dim3 grid((unsigned)(tiles * p.ngroups));
       const dim3 block(c.wm * c.wn * 64);
-      hipLaunchKernelGGL((gemm_tn_kgrouped_kernel<Mma, OUT, c.rows, c.cols, c.wm, c.wn>), grid,
-                         block, 0, s, p);
+      hipLaunchKernelGGL((gemm_tn_kernel<Mma, OUT, c.rows, c.cols, c.wm, c.wn, false, false,
+                                         TILE_GROUPED_K>), grid, block, 0, s, p);
       return hipGetLastError();
     }
   });

@@ -1,5 +1,5 @@
 // gemm_kgrouped_mxs: the K-grouped form of the tiled kernel (GemmArgs::kgrouped;
-// gemm_tn_kgrouped_kernel, gemm_kgrouped_kernels.h), the four codes of mxs_offers():
+// gemm_tn_kernel<.., TILE_GROUPED_K>, gemm_kgrouped_kernels.h), the four codes of mxs_offers():
 // block-scaled fp8 operands, bf16 / f16 / f32 out.
 #include "gemm_kgrouped_kernels.h"
 #include "gemm_entry.h"

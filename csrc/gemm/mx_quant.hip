@@ -26,6 +26,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
+#include "device_info.h"
 #include "gemm.h"
 #include "mx_cvt.h"
 #include "mx_quant_in.h"
@@ -35,8 +38,13 @@ namespace {
 
 constexpr int kMxqThreads = 256;
 
-template <int DT, bool FP4 = false>
-__global__ __launch_bounds__(kMxqThreads) void mx_quant_kernel(const MxQuantArgs a, int rows_pp) {
+// The gathering form (Args = MxQuantGatherArgs): output row r is the quantisation of x[src[r]] (a
+// routed layer's dispatch: the permuted 16-bit copy of x is never written). A lane reads its row's
+// index once per row, and an index outside [0, X) makes the row a zero row: zero data, scale byte
+// 127, nothing read.
+template <int DT, bool FP4, class Args = MxQuantArgs>
+__global__ __launch_bounds__(kMxqThreads) void mx_quant_kernel(const Args a, int rows_pp) {
+  constexpr bool GATHER = std::is_same<Args, MxQuantGatherArgs>::value;
   using In = MxqIn<DT>;
   constexpr int EPV = In::kElems;   // elements per 16-byte vector
   constexpr int LPB = 32 / EPV;     // lanes that share a 32-element block
@@ -51,43 +59,17 @@ __global__ __launch_bounds__(kMxqThreads) void mx_quant_kernel(const MxQuantArgs
   if (r_in >= rows_pp) return;  // whole blocks' lanes leave together (vpr % LPB == 0)
   const int64_t row_step = (int64_t)gridDim.x * rows_pp;
   for (int64_t row = (int64_t)blockIdx.x * rows_pp + r_in; row < a.R; row += row_step) {
-    const char* xr = (const char*)a.x + row * a.ldx * ESZ;
+    int64_t from = row;
+    bool real = true;  // (the lanes of a row agree)
+    if constexpr (GATHER) {
+      const int src = a.src[row];
+      real = src >= 0 && src < a.X;
+      from = real ? src : 0;
+    }
+    const char* xr = (const char*)a.x + from * a.ldx * ESZ;
     char* qr = (char*)a.q + row * a.ldq;
     uint8_t* sr = a.s + row * a.lds;
     for (int c = c0; c < vpr; c += kMxqThreads) {  // (lanes of a block share their trip count)
-      const mxq_u32x4 v = *(const mxq_u32x4*)(xr + (int64_t)c * 16);
-      mxq_rowwise_vec<DT, FP4>(v, qr + (int64_t)c * (FP4 ? EPV / 2 : EPV), sr + c / LPB,
-                               (tid & (LPB - 1)) == 0);
-    }
-  }
-}
-
-// The gathering flavour: output row r is the quantisation of x[src[r]] (a routed layer's dispatch:
-// the permuted 16-bit copy of x is never written). A lane reads its row's index once per row, and
-// an index outside [0, X) makes the row a zero row: zero data, scale byte 127, nothing read.
-template <int DT, bool FP4>
-__global__ __launch_bounds__(kMxqThreads) void mx_quant_gather_kernel(const MxQuantGatherArgs a,
-                                                                      int rows_pp) {
-  using In = MxqIn<DT>;
-  constexpr int EPV = In::kElems;
-  constexpr int LPB = 32 / EPV;
-  constexpr int ESZ = 16 / EPV;
-  const int vpr = a.K / EPV;
-  const int tid = threadIdx.x;
-  int r_in = 0, c0 = tid;
-  if (vpr < kMxqThreads) {
-    r_in = tid / vpr;
-    c0 = tid - r_in * vpr;
-  }
-  if (r_in >= rows_pp) return;
-  const int64_t row_step = (int64_t)gridDim.x * rows_pp;
-  for (int64_t row = (int64_t)blockIdx.x * rows_pp + r_in; row < a.R; row += row_step) {
-    const int from = a.src[row];
-    const bool real = from >= 0 && from < a.X;  // (the lanes of a row agree)
-    const char* xr = (const char*)a.x + (int64_t)(real ? from : 0) * a.ldx * ESZ;
-    char* qr = (char*)a.q + row * a.ldq;
-    uint8_t* sr = a.s + row * a.lds;
-    for (int c = c0; c < vpr; c += kMxqThreads) {
       mxq_u32x4 v = mxq_u32x4{0u, 0u, 0u, 0u};
       if (real) v = *(const mxq_u32x4*)(xr + (int64_t)c * 16);
       mxq_rowwise_vec<DT, FP4>(v, qr + (int64_t)c * (FP4 ? EPV / 2 : EPV), sr + c / LPB,
@@ -96,80 +78,49 @@ __global__ __launch_bounds__(kMxqThreads) void mx_quant_gather_kernel(const MxQu
   }
 }
 
-int mxq_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        n <= 0)
-      n = 256;
-  }
-  return n;
-}
-
-}  // namespace
-
-namespace {
-template <bool FP4>
-hipError_t mxq_launch(const MxQuantArgs& a, int din, hipStream_t s) {
+// Both forms: the same refusals and the same grid over the R output rows. Gathering, x needs
+// X >= 0 rows (X = 0: every row is a zero row and x is not read) and src is required.
+template <bool FP4, class Args>
+hipError_t mxq_launch(const Args& a, int din, hipStream_t s) {
+  constexpr bool GATHER = std::is_same<Args, MxQuantGatherArgs>::value;
   if (din != DT_F32 && din != DT_F16 && din != DT_BF16) return hipErrorInvalidValue;
   // fp4: q rows are K / 2 bytes, stored 4 (2) bytes per lane
   constexpr int KMOD = FP4 ? 256 : 128, QALIGN = FP4 ? 4 : 8;
   if (a.R < 0 || a.K <= 0 || a.K % KMOD) return hipErrorInvalidValue;
+  bool x_needed = true;
+  if constexpr (GATHER) {
+    if (a.X < 0) return hipErrorInvalidValue;
+    x_needed = a.X > 0;
+  }
   if (a.R == 0) return hipSuccess;
   const int esz = dtype_size(din);
-  if (a.x == nullptr || a.q == nullptr || a.s == nullptr || a.ldx < a.K ||
+  if ((a.x == nullptr && x_needed) || a.q == nullptr || a.s == nullptr || a.ldx < a.K ||
       a.ldq < (FP4 ? a.K / 2 : a.K) || a.lds < a.K / 32 || ((uintptr_t)a.x & 15) ||
       (a.ldx * esz) % 16 || ((uintptr_t)a.q & (QALIGN - 1)) || a.ldq % QALIGN)
     return hipErrorInvalidValue;
+  if constexpr (GATHER) {
+    if (a.src == nullptr) return hipErrorInvalidValue;
+  }
   const int vpr = a.K / (16 / esz);
   const int rows_pp = vpr < kMxqThreads ? kMxqThreads / vpr : 1;
   // eight 256-thread workgroups fill a CU's wave slots; the rest of the rows by grid stride
   int64_t grid = ((int64_t)a.R + rows_pp - 1) / rows_pp;
-  const int64_t cap = (int64_t)mxq_cus() * 8;
+  const int64_t cap = (int64_t)num_cus() * 8;
   if (grid > cap) grid = cap;
   auto go = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kMxqThreads), 0, s, a, rows_pp);
     return hipGetLastError();
   };
-  if (din == DT_F32) return go(mx_quant_kernel<DT_F32, FP4>);
-  if (din == DT_F16) return go(mx_quant_kernel<DT_F16, FP4>);
-  return go(mx_quant_kernel<DT_BF16, FP4>);
+  if (din == DT_F32) return go(mx_quant_kernel<DT_F32, FP4, Args>);
+  if (din == DT_F16) return go(mx_quant_kernel<DT_F16, FP4, Args>);
+  return go(mx_quant_kernel<DT_BF16, FP4, Args>);
 }
 
-// The same refusals and the same grid over the R output rows; x needs X >= 0 rows (X = 0: every
-// row is a zero row and x is not read).
-template <bool FP4>
-hipError_t mxq_gather_launch(const MxQuantGatherArgs& a, int din, hipStream_t s) {
-  if (din != DT_F32 && din != DT_F16 && din != DT_BF16) return hipErrorInvalidValue;
-  constexpr int KMOD = FP4 ? 256 : 128, QALIGN = FP4 ? 4 : 8;
-  if (a.R < 0 || a.X < 0 || a.K <= 0 || a.K % KMOD) return hipErrorInvalidValue;
-  if (a.R == 0) return hipSuccess;
-  const int esz = dtype_size(din);
-  if ((a.x == nullptr && a.X > 0) || a.src == nullptr || a.q == nullptr || a.s == nullptr ||
-      a.ldx < a.K || a.ldq < (FP4 ? a.K / 2 : a.K) || a.lds < a.K / 32 ||
-      ((uintptr_t)a.x & 15) || (a.ldx * esz) % 16 || ((uintptr_t)a.q & (QALIGN - 1)) ||
-      a.ldq % QALIGN)
-    return hipErrorInvalidValue;
-  const int vpr = a.K / (16 / esz);
-  const int rows_pp = vpr < kMxqThreads ? kMxqThreads / vpr : 1;
-  int64_t grid = ((int64_t)a.R + rows_pp - 1) / rows_pp;
-  const int64_t cap = (int64_t)mxq_cus() * 8;
-  if (grid > cap) grid = cap;
-  auto go = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kMxqThreads), 0, s, a, rows_pp);
-    return hipGetLastError();
-  };
-  if (din == DT_F32) return go(mx_quant_gather_kernel<DT_F32, FP4>);
-  if (din == DT_F16) return go(mx_quant_gather_kernel<DT_F16, FP4>);
-  return go(mx_quant_gather_kernel<DT_BF16, FP4>);
-}
 }  // namespace
 
 hipError_t mx_quantize_gather_launch(const MxQuantGatherArgs& a, int din, bool fp4,
                                      hipStream_t s) {
-  return fp4 ? mxq_gather_launch<true>(a, din, s) : mxq_gather_launch<false>(a, din, s);
+  return fp4 ? mxq_launch<true>(a, din, s) : mxq_launch<false>(a, din, s);
 }
 
 hipError_t mx_quantize_launch(const MxQuantArgs& a, int din, hipStream_t s) {

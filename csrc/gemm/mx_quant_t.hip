@@ -34,12 +34,36 @@
 //
 // The grid is one workgroup per tile, column tiles fastest (two-way: permuted within groups of
 // 16 or 32 workgroups, see the kernel); no grid cap, no scratch.
+//
+// The grouped form (Args = MxQuantTGroupedArgs, one-way) is the same kernel template behind
+// another prologue: x[T, C], its rows sorted into E groups by a device array of offsets ->
+// qt[C, cap], st[C, cap / 32] in the padded K layout of a K-grouped GEMM (tile_map.h
+// kgrouped_range): group g's blocks start at the group's first row, run down the columns of x and
+// fill the columns [k0_g, k0_g + kl_g) of qt, the group's last tile zero-extended. Byte for byte
+// that is the plain form's output for the group's rows padded with zero rows to a multiple of TR
+// (ddlb_amd/ops/mx.py quantize_mx_t_grouped_reference is the specification). An all-zero block
+// gets the scale byte 127 and zero data (mx_cvt.h), so the padding contributes exact zeros to a
+// contraction over it. The prologue:
+//   * the grid is the bound (T / TR + E) * ctiles of tile_map.h: a workgroup finds its
+//     (group, row tile of the group) with grouped_tile (BM = TR), or finds none and returns
+//     before the barrier; a tile starts at any row of x, not at a multiple of TR, and has nrows
+//     source rows left in its group: step 1 predicates a row at or past that off (it stands for
+//     zeros, as a vector past column C does);
+//   * step 2's destination column d0 is TR times the LAUNCH-WIDE row tile index, which is k0_g
+//     plus the tile's offset in the group, below the capacity because the grid is;
+//   * stacked form (stacked_rows = R > 0): group g is written to its own slab, from column 0, and
+//     a tile at or past row R of the group is dropped: with x = w.reshape(E * N, K), offsets
+//     arange(E + 1) * N and R = N, one launch writes the column-wise quantisation [E, K, N] of
+//     every expert's weight.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "gemm.h"
 #include "mx_cvt.h"
 #include "mx_quant_in.h"
+#include "tile_map.h"
 
 namespace ddlb {
 namespace {
@@ -48,10 +72,12 @@ constexpr int kMxtThreads = 256;
 constexpr int kMxtCols = 64;  // tile width in elements
 
 // (waves per SIMD: without the hint the register allocator spends 240 VGPRs on three of the
-// twelve instantiations and halves what their LDS footprint would let a CU hold)
-template <int DT, bool FP4, bool TWO>
+// twelve plain instantiations and halves what their LDS footprint would let a CU hold)
+template <int DT, bool FP4, bool TWO, class Args = MxQuantTArgs>
 __global__ __launch_bounds__(kMxtThreads) __attribute__((amdgpu_waves_per_eu(4, 8)))
-void mx_quant_t_kernel(const MxQuantTArgs a, int ctiles) {
+void mx_quant_t_kernel(const Args a, int ctiles) {
+  constexpr bool GROUPED = std::is_same<Args, MxQuantTGroupedArgs>::value;
+  static_assert(!(GROUPED && TWO), "the grouped form is one-way");
   using In = MxqIn<DT>;
   constexpr int EPV = In::kElems;           // elements per 16-byte vector
   constexpr int ESZ = 16 / EPV;
@@ -64,19 +90,41 @@ void mx_quant_t_kernel(const MxQuantTArgs a, int ctiles) {
   __shared__ mxq_u32x4 tile[TR * VPR];      // 16, 32 or 64 KiB
 
   const int tid = threadIdx.x;
-  unsigned bid = blockIdx.x;
-  if constexpr (TWO) {
-    // A tile's row of q is 64 bytes (fp4: 32), half (a quarter) of a 128-byte line, and workgroups
-    // b and b + 8 share an XCD and its L2 (observed dispatch order; only speed rests on it). So
-    // within every whole group of 8 P workgroups, P = 2 (4), the P column tiles that complete a
-    // line go to workgroups 8 apart and the line leaves one L2 whole. ctiles % P == 0.
-    constexpr unsigned P = FP4 ? 4 : 2;
-    const unsigned grp = bid / (8 * P), i = bid % (8 * P);
-    if ((grp + 1) * (8 * P) <= gridDim.x) bid = grp * (8 * P) + (i % 8) * P + i / 8;
+  int64_t r0;                   // the tile's first row in x
+  int64_t d0;                   // ... and its first column in qt (st: d0 / 32)
+  int c0;                       // the tile's first column in x
+  int nrows = TR;               // grouped: rows of x from r0 to its group's end (> 0)
+  char* qt = (char*)a.qt;
+  uint8_t* st = a.st;
+  if constexpr (GROUPED) {
+    GroupTile t;
+    if (!grouped_tile(a.offs, a.T, a.ngroups, TR, ctiles, (int)blockIdx.x, t)) return;
+    const int tr0 = t.tm * TR;  // the tile's first row within the group
+    nrows = t.rows - tr0;
+    r0 = (int64_t)t.row0 + tr0;
+    c0 = t.tn * kMxtCols;
+    d0 = (int64_t)((int)blockIdx.x / ctiles) * TR;  // the padded layout's column
+    if (a.stacked_rows > 0) {                       // ... or the group's slab
+      if (tr0 >= a.stacked_rows) return;
+      d0 = tr0;
+      qt += (int64_t)t.g * a.qt_gstride;
+      st += (int64_t)t.g * a.st_gstride;
+    }
+  } else {
+    unsigned bid = blockIdx.x;
+    if constexpr (TWO) {
+      // A tile's row of q is 64 bytes (fp4: 32), half (a quarter) of a 128-byte line, and
+      // workgroups b and b + 8 share an XCD and its L2 (observed dispatch order; only speed rests
+      // on it). So within every whole group of 8 P workgroups, P = 2 (4), the P column tiles that
+      // complete a line go to workgroups 8 apart and the line leaves one L2 whole.
+      // ctiles % P == 0.
+      constexpr unsigned P = FP4 ? 4 : 2;
+      const unsigned grp = bid / (8 * P), i = bid % (8 * P);
+      if ((grp + 1) * (8 * P) <= gridDim.x) bid = grp * (8 * P) + (i % 8) * P + i / 8;
+    }
+    r0 = d0 = (int64_t)(bid / (unsigned)ctiles) * TR;
+    c0 = (int)(bid % (unsigned)ctiles) * kMxtCols;
   }
-  const int ct = (int)(bid % (unsigned)ctiles);
-  const int64_t r0 = (int64_t)(bid / (unsigned)ctiles) * TR;
-  const int c0 = ct * kMxtCols;
 
   // 1. global -> registers (all loads in flight), then -> LDS (and the row-wise outputs)
   mxq_u32x4 v[NV];
@@ -86,7 +134,7 @@ void mx_quant_t_kernel(const MxQuantTArgs a, int ctiles) {
     const int r = idx / VPR, k = idx % VPR;
     const int col = c0 + k * EPV;  // C % EPV == 0: a vector lies wholly inside or outside
     v[i] = mxq_u32x4{0u, 0u, 0u, 0u};
-    if (TWO || col < a.C)
+    if ((TWO || col < a.C) && (!GROUPED || r < nrows))
       v[i] = *(const mxq_u32x4*)((const char*)a.x + ((r0 + r) * a.ldx + col) * ESZ);
   }
 #pragma unroll
@@ -131,7 +179,7 @@ void mx_quant_t_kernel(const MxQuantTArgs a, int ctiles) {
         w[j] = t;
       }
       if (ok)
-        *(mxq_u32x4*)((char*)a.qt + (int64_t)col * a.ldqt + (r0 + 32 * b) / 2) =
+        *(mxq_u32x4*)(qt + (int64_t)col * a.ldqt + (d0 + 32 * b) / 2) =
             mxq_u32x4{w[0], w[1], w[2], w[3]};
     } else {
       unsigned w[8];
@@ -139,7 +187,7 @@ void mx_quant_t_kernel(const MxQuantTArgs a, int ctiles) {
       for (int j = 0; j < 8; ++j)
         w[j] = mx_cvt4_e4m3(f[4 * j], f[4 * j + 1], f[4 * j + 2], f[4 * j + 3], e);
       if (ok) {
-        mxq_u32x4* dst = (mxq_u32x4*)((char*)a.qt + (int64_t)col * a.ldqt + r0 + 32 * b);
+        mxq_u32x4* dst = (mxq_u32x4*)(qt + (int64_t)col * a.ldqt + d0 + 32 * b);
         dst[0] = mxq_u32x4{w[0], w[1], w[2], w[3]};
         dst[1] = mxq_u32x4{w[4], w[5], w[6], w[7]};
       }
@@ -149,38 +197,75 @@ void mx_quant_t_kernel(const MxQuantTArgs a, int ctiles) {
     sw |= (unsigned)__shfl_xor((int)sw, 1);
     sw |= (unsigned)__shfl_xor((int)sw, 2);
     if (ok && (b & 3) == 0)
-      *(unsigned*)(a.st + (int64_t)col * a.ldst + r0 / 32 + b) = sw;
+      *(unsigned*)(st + (int64_t)col * a.ldst + d0 / 32 + b) = sw;
   }
 }
 
-template <bool FP4, bool TWO>
-hipError_t mxt_launch(const MxQuantTArgs& a, int din, hipStream_t s) {
-  if (din != DT_F32 && din != DT_F16 && din != DT_BF16) return hipErrorInvalidValue;
-  constexpr int MOD = FP4 ? 256 : 128;      // R (and, two-way, C) as a GEMM's K
-  constexpr int SALIGN = FP4 ? 8 : 4;       // st: one word per tile and row
-  constexpr int QALIGN = FP4 ? 4 : 8;       // q: the row-wise kernel's packed store
-  const int esz = dtype_size(din);
-  if (a.R < 0 || a.C < 0 || a.R % MOD || ((int64_t)a.C * esz) % 16) return hipErrorInvalidValue;
-  if (TWO && a.C % MOD) return hipErrorInvalidValue;
-  if (a.R == 0 || a.C == 0) return hipSuccess;
-  if (a.x == nullptr || a.qt == nullptr || a.st == nullptr || a.ldx < a.C ||
-      a.ldqt < (FP4 ? a.R / 2 : a.R) || a.ldst < a.R / 32 || ((uintptr_t)a.x & 15) ||
-      (a.ldx * esz) % 16 || ((uintptr_t)a.qt & 15) || a.ldqt % 16 ||
-      ((uintptr_t)a.st & (SALIGN - 1)) || a.ldst % SALIGN)
-    return hipErrorInvalidValue;
-  if (TWO && (a.q == nullptr || a.s == nullptr || a.ldq < (FP4 ? a.C / 2 : a.C) ||
-              a.lds < a.C / 32 || ((uintptr_t)a.q & (QALIGN - 1)) || a.ldq % QALIGN))
-    return hipErrorInvalidValue;
-  const int ctiles = (a.C + kMxtCols - 1) / kMxtCols;
-  const int64_t grid = (int64_t)(a.R / (FP4 ? 256 : 128)) * ctiles;
+// What the two launches below check alike. The input: a dtype with a 16-byte vector load, C
+// columns that are whole vectors.
+bool mxt_input_ok(int din, int C) {
+  if (din != DT_F32 && din != DT_F16 && din != DT_BF16) return false;
+  return C >= 0 && ((int64_t)C * dtype_size(din)) % 16 == 0;
+}
+
+// x[., C] and qt, st with `cols` quantised columns: present, wide enough, aligned for the
+// kernel's 16-byte loads and stores and for st's one word per tile and row.
+template <bool FP4, class Args>
+bool mxt_operands_ok(const Args& a, int din, int64_t cols) {
+  constexpr int SALIGN = FP4 ? 8 : 4;
+  return a.x != nullptr && a.qt != nullptr && a.st != nullptr && a.ldx >= a.C &&
+         a.ldqt >= (FP4 ? cols / 2 : cols) && a.ldst >= cols / 32 && !((uintptr_t)a.x & 15) &&
+         (a.ldx * dtype_size(din)) % 16 == 0 && !((uintptr_t)a.qt & 15) && a.ldqt % 16 == 0 &&
+         !((uintptr_t)a.st & (SALIGN - 1)) && a.ldst % SALIGN == 0;
+}
+
+// `grid` workgroups (a 31-bit grid, or refused) of the input dtype's kernel
+template <bool FP4, bool TWO, class Args>
+hipError_t mxt_go(const Args& a, int din, int64_t grid, int ctiles, hipStream_t s) {
   if (grid > 0x7FFFFFFF) return hipErrorInvalidValue;
   auto go = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kMxtThreads), 0, s, a, ctiles);
     return hipGetLastError();
   };
-  if (din == DT_F32) return go(mx_quant_t_kernel<DT_F32, FP4, TWO>);
-  if (din == DT_F16) return go(mx_quant_t_kernel<DT_F16, FP4, TWO>);
-  return go(mx_quant_t_kernel<DT_BF16, FP4, TWO>);
+  if (din == DT_F32) return go(mx_quant_t_kernel<DT_F32, FP4, TWO, Args>);
+  if (din == DT_F16) return go(mx_quant_t_kernel<DT_F16, FP4, TWO, Args>);
+  return go(mx_quant_t_kernel<DT_BF16, FP4, TWO, Args>);
+}
+
+template <bool FP4, bool TWO>
+hipError_t mxt_launch(const MxQuantTArgs& a, int din, hipStream_t s) {
+  constexpr int MOD = FP4 ? 256 : 128;      // R (and, two-way, C) as a GEMM's K
+  constexpr int QALIGN = FP4 ? 4 : 8;       // q: the row-wise kernel's packed store
+  if (!mxt_input_ok(din, a.C) || a.R < 0 || a.R % MOD) return hipErrorInvalidValue;
+  if (TWO && a.C % MOD) return hipErrorInvalidValue;
+  if (a.R == 0 || a.C == 0) return hipSuccess;
+  if (!mxt_operands_ok<FP4>(a, din, a.R)) return hipErrorInvalidValue;
+  if (TWO && (a.q == nullptr || a.s == nullptr || a.ldq < (FP4 ? a.C / 2 : a.C) ||
+              a.lds < a.C / 32 || ((uintptr_t)a.q & (QALIGN - 1)) || a.ldq % QALIGN))
+    return hipErrorInvalidValue;
+  const int ctiles = (a.C + kMxtCols - 1) / kMxtCols;
+  return mxt_go<FP4, TWO>(a, din, (int64_t)(a.R / MOD) * ctiles, ctiles, s);
+}
+
+template <bool FP4>
+hipError_t mxtg_launch(const MxQuantTGroupedArgs& a, int din, hipStream_t s) {
+  constexpr int MOD = FP4 ? 256 : 128;      // the tile rows: a K-grouped GEMM's K-tile
+  constexpr int SALIGN = FP4 ? 8 : 4;
+  if (!mxt_input_ok(din, a.C) || a.T < 0) return hipErrorInvalidValue;
+  if (a.ngroups < 1 || a.ngroups > kMaxGroups) return hipErrorInvalidValue;
+  if (a.stacked_rows < 0 || a.stacked_rows % MOD) return hipErrorInvalidValue;
+  if (a.T == 0 || a.C == 0) return hipSuccess;
+  const bool stacked = a.stacked_rows > 0;
+  const int64_t cols = stacked ? a.stacked_rows : kgrouped_capacity(a.T, a.ngroups, MOD);
+  if (!mxt_operands_ok<FP4>(a, din, cols) || a.offs == nullptr || ((uintptr_t)a.offs & 3))
+    return hipErrorInvalidValue;
+  if (stacked && (a.qt_gstride < 0 || a.qt_gstride % 16 || a.st_gstride < 0 ||
+                  a.st_gstride % SALIGN ||
+                  (a.ngroups > 1 && (a.qt_gstride < (int64_t)a.C * a.ldqt ||
+                                     a.st_gstride < (int64_t)a.C * a.ldst))))
+    return hipErrorInvalidValue;
+  const int ctiles = (a.C + kMxtCols - 1) / kMxtCols;
+  return mxt_go<FP4, false>(a, din, grouped_grid_bound(a.T, a.ngroups, MOD, ctiles), ctiles, s);
 }
 
 }  // namespace
@@ -189,6 +274,11 @@ hipError_t mx_quantize_t_launch(const MxQuantTArgs& a, int din, bool fp4, bool t
                                 hipStream_t s) {
   if (fp4) return two ? mxt_launch<true, true>(a, din, s) : mxt_launch<true, false>(a, din, s);
   return two ? mxt_launch<false, true>(a, din, s) : mxt_launch<false, false>(a, din, s);
+}
+
+hipError_t mx_quantize_t_grouped_launch(const MxQuantTGroupedArgs& a, int din, bool fp4,
+                                        hipStream_t s) {
+  return fp4 ? mxtg_launch<true>(a, din, s) : mxtg_launch<false>(a, din, s);
 }
 
 }  // namespace ddlb

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "device_info.h"
 #include "gemm.h"
 #include "mx_quant_in.h"
 
@@ -72,22 +73,10 @@ inline bool row_ptr_ok(const void* p, int64_t ld, int64_t cols, int esz) {
   return p != nullptr && ld >= cols && ((uintptr_t)p & 15) == 0 && (ld * esz) % 16 == 0;
 }
 
-inline int row_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        n <= 0)
-      n = 256;
-  }
-  return n;
-}
-
 // Workgroups for `rows` rows taken rows_pp per pass, grid-striding: at most 8 per CU.
 inline unsigned row_grid(int64_t rows, int rows_pp) {
   int64_t grid = (rows + rows_pp - 1) / rows_pp;
-  const int64_t cap = (int64_t)row_cus() * 8;
+  const int64_t cap = (int64_t)num_cus() * 8;
   if (grid > cap) grid = cap;
   return (unsigned)(grid < 1 ? 1 : grid);
 }

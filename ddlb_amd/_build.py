@@ -54,7 +54,6 @@ SOURCES = [  # heaviest translation units first (the parallel build's critical p
     "gemm/gemm_mx4.hip",
     "gemm/mx_quant.hip",
     "gemm/mx_quant_t.hip",
-    "gemm/mx_quant_t_grouped.hip",
     "gemm/gemm_generic.hip",
     "gemm/gemm_mfma.hip",
     "gemm/gemm_grouped.hip",
@@ -70,57 +69,10 @@ SOURCES = [  # heaviest translation units first (the parallel build's critical p
     "bindings.cpp",
 ]
 HEADERS = ["gemm/gemm.h", "gemm/gemm_kernels.h", "gemm/gemm_entry.h", "gemm/tile_map.h",
-           "gemm/mx_cvt.h", "gemm/mx_quant_in.h", "gemm/row_io.h", "gemm/glu_act.h",
-           "gemm/gemm_grouped_kernels.h", "gemm/gemm_kgrouped_kernels.h", "moe/moe.h",
-           "moe/moe_route_map.h", "runtime/kernels.h", "comm/comm.h", "runtime/plan.h", "runtime/plan_ir.h"]
-
-# The grouped tiled kernel (gemm/gemm_grouped_kernels.h) runs the body of gemm_tn_kernel, the same
-# text: grouped_body() copies it out of gemm_kernels.h into GEN/gemm_tn_grouped_body.gen.h with one
-# line replaced (the choice of the tile), so gemm_kernels.h itself stays as it is.
-GEN = os.path.join(BUILD, "gen")
-GROUPED_BODY = "gemm_tn_grouped_body.gen.h"
-_TILED_SIGNATURE = ("template <class Mma, int OUT, int BM, int BN, int WM, int WN, "
-                    "bool ILV = false, bool GLU = false>\n"
-                    "__global__ __launch_bounds__(WM* WN * 64) void gemm_tn_kernel("
-                    "const GemmArgs p) {\n")
-_TILED_END = "\n}\n\n// ---------------------------------------------------------------- counted waits"
-_TILE_CHOICE = ("  const int wg = tile_index(p, nwg);\n", "  const int wg = wg_group;\n")
-
-
-def grouped_body(header_text: str) -> str:
-    """The body of ``gemm_tn_kernel`` in ``gemm_kernels.h`` (the lines between its signature and
-    its closing brace), with the line that chooses the tile replaced by the grouped kernel's.
-    Each anchor must occur exactly once: an edit of the header that breaks one fails the build."""
-    for what, pat in (("signature", _TILED_SIGNATURE), ("end", _TILED_END)):
-        if header_text.count(pat) != 1:
-            raise RuntimeError(f"gemm_kernels.h: the {what} of gemm_tn_kernel was found "
-                               f"{header_text.count(pat)} times, not once")
-    i = header_text.index(_TILED_SIGNATURE) + len(_TILED_SIGNATURE)
-    j = header_text.index(_TILED_END, i)
-    body = header_text[i:j] + "\n"
-    if body.count(_TILE_CHOICE[0]) != 1:
-        raise RuntimeError("gemm_kernels.h: gemm_tn_kernel chooses its tile in "
-                           f"{body.count(_TILE_CHOICE[0])} lines, not one")
-    return ("// Generated by ddlb_amd/_build.py from gemm_kernels.h: the body of gemm_tn_kernel "
-            "with its tile\n// choice replaced (see gemm_grouped_kernels.h). Do not edit.\n"
-            + body.replace(*_TILE_CHOICE))
-
-
-def _generate() -> str:
-    """Write GEN/gemm_tn_grouped_body.gen.h if its content changed; -> its text."""
-    os.makedirs(GEN, exist_ok=True)
-    with open(os.path.join(CSRC, "gemm", "gemm_kernels.h")) as f:
-        text = grouped_body(f.read())
-    path = os.path.join(GEN, GROUPED_BODY)
-    old = None
-    if os.path.exists(path):
-        with open(path) as f:
-            old = f.read()
-    if old != text:
-        with open(path + ".tmp", "w") as f:
-            f.write(text)
-        os.replace(path + ".tmp", path)
-    return text
+           "gemm/device_info.h", "gemm/mx_cvt.h", "gemm/mx_quant_in.h", "gemm/row_io.h",
+           "gemm/glu_act.h", "gemm/gemm_grouped_kernels.h", "gemm/gemm_kgrouped_kernels.h",
+           "moe/moe.h", "moe/moe_route_map.h", "runtime/kernels.h", "comm/comm.h",
+           "runtime/plan.h", "runtime/plan_ir.h"]
 
 
 def ext_path() -> str:
@@ -138,7 +90,7 @@ def _hipcc() -> str:
 def _includes():
     import pybind11
 
-    inc = [CSRC, GEN, sysconfig.get_paths()["include"], pybind11.get_include(),
+    inc = [CSRC, sysconfig.get_paths()["include"], pybind11.get_include(),
            os.path.join(ROCM, "include")]
     try:  # only ATen/dlpack.h is used from torch's headers
         import importlib.util
@@ -213,7 +165,6 @@ def build(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
     of the sources they were built from (``<file>.sha256``): whatever differs from the tree's
     content is rebuilt, so a checkout or copy that resets file times cannot leave a stale .so."""
     os.makedirs(BUILD, exist_ok=True)
-    _generate()  # (a function of gemm_kernels.h, which every object's digest covers)
     out = ext_path()
     digest = source_digest()
     jobs = jobs or min(len(SOURCES), max(1, os.cpu_count() or 4), 8)

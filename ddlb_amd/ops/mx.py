@@ -661,7 +661,7 @@ def _check_quant_t_grouped(x, offsets, fmt: str, out=None, stacked_rows: int = 0
 
 def quantize_mx_t_grouped(x, offsets, *, fmt: str = "mx", out=None, stacked_rows: int = 0,
                           stream=None):
-    """The HIP grouped transposing quantiser (``csrc/gemm/mx_quant_t_grouped.hip``): ``x [T, C]``
+    """The HIP transposing quantiser's grouped form (``csrc/gemm/mx_quant_t.hip``): ``x [T, C]``
     bf16 / f16 / f32 with its rows sorted into ``E`` groups by ``offsets`` (int32 ``[E + 1]`` on
     ``x``'s device, read by the kernel only and clamped as a grouped GEMM clamps them: no host
     sync) -> ``(qt, st)`` in the padded K layout of :func:`ddlb_amd.ops.gemm.gemm_kgrouped`:

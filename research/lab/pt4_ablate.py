@@ -636,7 +636,7 @@ def build(variant: str, verbose: bool = False) -> str:
     if os.path.exists(out) and os.path.exists(stamp) and open(stamp).read().strip() == dig:
         return out
     # (-I csrc/gemm after the variant's own headers: what the product header includes beyond the
-    # three written above, mx_cvt.h, comes from the working tree)
+    # three written above, mx_cvt.h and device_info.h, comes from the working tree)
     cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-shared",
            "--offload-arch=gfx950", f"-I{d}", f"-I{CSRC}", os.path.join(HERE, "pt4_lab.hip"),
            "-o", out]

@@ -242,30 +242,3 @@ def test_mx_moe_reference_equals_the_per_expert_chain(fmt):
         assert torch.equal(got[mask], want), e
         seen |= mask
     assert bool(seen.all()) and float(got.abs().max()) > 0
-
-
-def test_grouped_body_is_the_tiled_kernels_text():
-    """The build's copy of ``gemm_tn_kernel``'s body for the grouped kernel: the header's own
-    lines with exactly the tile choice replaced, and a loud failure when an anchor is missing."""
-    import os
-
-    from ddlb_amd import _build
-
-    with open(os.path.join(_build.CSRC, "gemm", "gemm_kernels.h")) as f:
-        header = f.read()
-    body = _build.grouped_body(header)
-    lines = [ln for ln in body.splitlines() if not ln.startswith("// ")]
-    assert lines.count("  const int wg = wg_group;") == 1 and "tile_index(" not in body
-    assert "  __shared__ __attribute__((aligned(1024))) char smem[2 * STAGE];" in lines
-    assert "__global__" not in body and "gemm_tn_t8_kernel" not in body
-    # every other line stands in the header, in the same order
-    rest = [ln for ln in lines if ln != "  const int wg = wg_group;"]
-    at = 0
-    for ln in rest:
-        at = header.index(ln + "\n", at) + len(ln) + 1
-    assert body.count("{") == body.count("}")
-    with pytest.raises(RuntimeError, match="signature of gemm_tn_kernel was found 0 times"):
-        _build.grouped_body(header.replace("void gemm_tn_kernel(", "void gemm_tn_kernel2("))
-    with pytest.raises(RuntimeError, match="chooses its tile in 0 lines"):
-        _build.grouped_body(header.replace("const int wg = tile_index(p, nwg);",
-                                           "const int wg = tile_index(p, nwg) + 0;", 1))
