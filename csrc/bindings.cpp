@@ -15,6 +15,7 @@
 
 #include "comm/comm.h"
 #include "gemm/gemm.h"
+#include "gemm/gemm_skinny.h"
 #include "gemm/glu_act.h"
 #include "moe/moe.h"
 #include "moe/moe_route_map.h"
@@ -240,6 +241,38 @@ PYBIND11_MODULE(_C, m) {
         py::arg("M"), py::arg("N"), py::arg("K"), py::arg("din"), py::arg("dout"),
         py::arg("tile") = 0, py::arg("stream") = 0, py::arg("a_scale") = 0,
         py::arg("b_scale") = 0, py::arg("a_scale_ld") = 0, py::arg("b_scale_ld") = 0);
+  // Skinny-M block-scaled GEMM (gemm_skinny.h): dense, or grouped with offs / ngroups as
+  // gemm_grouped takes them; ksplit K-slices (0: automatic) through the f32 workspace ws.
+  m.attr("SKINNY_NR") = kSkinnyNR;
+  m.attr("SKINNY_PANEL") = kSkinnyPanel;
+  m.def("gemm_skinny",
+        [](uintptr_t a, uintptr_t w, uintptr_t c, int64_t lda, int64_t ldw, int64_t ldc, int M,
+           int N, int K, int din, int dout, uintptr_t a_scale, uintptr_t w_scale,
+           int64_t a_scale_ld, int64_t w_scale_ld, int act, int ksplit, uintptr_t ws,
+           uintptr_t offs, int ngroups, int64_t w_gstride, int64_t w_scale_gstride,
+           uintptr_t stream) {
+          SkinnyArgs p;
+          p.a = (const void*)a; p.w = (const void*)w; p.c = (void*)c;
+          p.a_scale = (const uint8_t*)a_scale; p.w_scale = (const uint8_t*)w_scale;
+          p.lda = lda; p.ldw = ldw; p.ldc = ldc;
+          p.a_scale_ld = a_scale_ld; p.w_scale_ld = w_scale_ld;
+          p.M = M; p.N = N; p.K = K;
+          p.act = act; p.ksplit = ksplit; p.ws = (float*)ws;
+          p.offs = (const int*)offs; p.ngroups = ngroups;
+          p.w_gstride = w_gstride; p.w_scale_gstride = w_scale_gstride;
+          check(gemm_skinny_launch(p, din, dout, (hipStream_t)stream), "gemm_skinny");
+        },
+        py::arg("a"), py::arg("w"), py::arg("c"), py::arg("lda"), py::arg("ldw"), py::arg("ldc"),
+        py::arg("M"), py::arg("N"), py::arg("K"), py::arg("din"), py::arg("dout"),
+        py::arg("a_scale"), py::arg("w_scale"), py::arg("a_scale_ld"), py::arg("w_scale_ld"),
+        py::arg("act") = 0, py::arg("ksplit") = 0, py::arg("ws") = 0, py::arg("offs") = 0,
+        py::arg("ngroups") = 0, py::arg("w_gstride") = 0, py::arg("w_scale_gstride") = 0,
+        py::arg("stream") = 0);
+  // the launch arithmetic of gemm_skinny.h: (strips, the automatic slice count)
+  m.def("skinny_plan", [](int N, int nk, int groups, int cus) {
+    const int strips = skinny_strips(N);
+    return std::make_tuple(strips, skinny_auto_slices(strips, nk, groups, cus));
+  });
   m.def("mx_quantize_t_grouped",  // x[T, C], rows grouped by offs -> qt / st in the padded K
         // layout of gemm_kgrouped, or (stacked_rows > 0) one [C, R] slab per group
         [](uintptr_t x, uintptr_t qt, uintptr_t st, uintptr_t offs, int ngroups, int64_t ldx,

@@ -1,0 +1,101 @@
+// Skinny-M block-scaled GEMM (csrc/gemm/gemm_skinny.hip): C[M, N] = A[M, K] W[N, K]^T for decode
+// shapes, M (or the rows of an expert) <= 64, where the work is one pass over the weights. Its
+// arguments and the host-side arithmetic of its launch: strips, K-slices, the automatic slice
+// count and the workspace, usable from host code (ddlb_amd/ops/gemm.py states the same rules).
+//
+// A workgroup is 4 waves, each owning kSkinnyNR 16-row tiles of W: a strip of 64 kSkinnyNR weight
+// rows. It walks one K-slice of its strip; the grid is strips x S x groups. S > 1 writes f32
+// partials [S, rows, N] that a second kernel sums in the order s = 0 .. S - 1 (no atomics: two
+// runs write the same bytes). Any M is correct; past 64 rows the weights are streamed once per
+// 64 rows, which is what the tiled kernel is for.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "gemm.h"
+
+namespace ddlb {
+
+// Compile-time choices, picked by measurement (docs/RESULTS.md "Skinny-M GEMM").
+#ifndef DDLB_SKINNY_NR
+#define DDLB_SKINNY_NR 2
+#endif
+#ifndef DDLB_SKINNY_PANEL
+#define DDLB_SKINNY_PANEL 4
+#endif
+constexpr int kSkinnyNR = DDLB_SKINNY_NR;        // 16-row W tiles per wave (1 or 2)
+constexpr int kSkinnyPanel = DDLB_SKINNY_PANEL;  // K-tiles per A panel in LDS = W K-tiles in flight
+constexpr int kSkinnyWaves = 4;
+constexpr int kSkinnyStrip = 16 * kSkinnyWaves * kSkinnyNR;  // W rows per workgroup
+constexpr int kSkinnyMaxSlices = 16;             // the cap of the automatic slice count
+static_assert(kSkinnyNR == 1 || kSkinnyNR == 2, "one or two W tiles per wave");
+
+// Operand and scale layouts are GemmArgs' (gemm.h): leading dimensions in ELEMENTS (fp4: two per
+// byte), scale rows in BYTES, one E8M0 byte per 32 K elements. din DT_FP8 (K % 128 == 0) or DT_FP4
+// (K % 256 == 0); dout bf16 / f16 / f32. Operand rows 16-byte aligned; scale base and row stride
+// multiples of 4 (fp4: 8). Any N >= 1; M == 0 launches nothing.
+struct SkinnyArgs {
+  const void* a = nullptr;
+  const void* w = nullptr;
+  void* c = nullptr;
+  const uint8_t* a_scale = nullptr;
+  const uint8_t* w_scale = nullptr;
+  int64_t lda = 0, ldw = 0, ldc = 0;
+  int64_t a_scale_ld = 0, w_scale_ld = 0;
+  int M = 0, N = 0, K = 0;  // grouped: M = T, the rows of a the launch may touch
+  int act = 0;              // ACT_* (gemm.h), applied to the f32 sum before the one rounding
+  // K-slices: 0 = automatic (skinny_auto_slices with the device's CUs), else 1 .. nk. With S > 1
+  // ws holds S * M * N floats (skinny_workspace_floats), 16-byte aligned.
+  int ksplit = 0;
+  float* ws = nullptr;
+  // Grouped form (optional): offs is a DEVICE array of ngroups + 1 int32 row offsets, clamped on
+  // the device as GemmArgs::grp_offs is; group g multiplies its rows by the weight at
+  // w + g * w_gstride ELEMENTS under the scales at w_scale + g * w_scale_gstride BYTES. Rows
+  // outside [o'[0], o'[ngroups]) are not written. 1 <= ngroups <= kMaxGroups.
+  const int* offs = nullptr;
+  int ngroups = 0;
+  int64_t w_gstride = 0, w_scale_gstride = 0;
+};
+hipError_t gemm_skinny_launch(const SkinnyArgs& p, int din, int dout, hipStream_t s);
+
+// strips of N weight rows (the last one may be ragged)
+__host__ __device__ inline int skinny_strips(int N) {
+  return (int)(((int64_t)N + kSkinnyStrip - 1) / kSkinnyStrip);
+}
+
+// K-tiles (128 bytes of a row: 128 fp8 or 256 fp4 elements) of slice s of S: contiguous, in
+// order, covering [0, nk) exactly once; nk need not divide by S, and S <= nk leaves none empty
+__host__ __device__ inline void skinny_slice(int nk, int S, int s, int& k0, int& k1) {
+  k0 = (int)((int64_t)nk * s / S);
+  k1 = (int)((int64_t)nk * (s + 1) / S);
+}
+
+// the automatic slice count: the smallest S <= min(nk, 16) whose grid has two workgroups per CU
+__host__ __device__ inline int skinny_auto_slices(int strips, int nk, int groups, int cus) {
+  const int cap = nk < kSkinnyMaxSlices ? nk : kSkinnyMaxSlices;
+  for (int S = 1; S < cap; ++S)
+    if ((int64_t)strips * S * groups >= 2 * (int64_t)cus) return S;
+  return cap;
+}
+
+// floats of the workspace of S slices over `rows` rows (M, grouped: T)
+__host__ __device__ inline int64_t skinny_workspace_floats(int S, int rows, int N) {
+  return S > 1 ? (int64_t)S * rows * N : 0;
+}
+
+// Group g's clamped row range [r0, r1) (tile_map.h grouped_clamp: o'[0] = clamp(o[0], 0, T),
+// o'[j + 1] = clamp(o[j + 1], o'[j], T), which is the running maximum of the offsets clamped to
+// [0, T]); g = -1 gives [o'[0], o'[E]) with E = last. Uniform over a workgroup: scalar loads.
+__host__ __device__ inline void skinny_group_rows(const int* offs, int T, int g, int last,
+                                                  int& r0, int& r1) {
+  const int first = offs[0] < 0 ? 0 : offs[0];
+  int run = first;
+  const int upto = g < 0 ? last : g;
+  for (int j = 1; j <= upto; ++j) run = offs[j] > run ? offs[j] : run;
+  r0 = g < 0 ? first : run;
+  r1 = g < 0 ? run : (offs[g + 1] > run ? offs[g + 1] : run);
+  r0 = r0 < T ? r0 : T;
+  r1 = r1 < T ? r1 : T;
+}
+
+}  // namespace ddlb

@@ -52,6 +52,7 @@ SOURCES = [  # heaviest translation units first (the parallel build's critical p
     "gemm/gemm_mx.hip",
     "gemm/gemm_mxs.hip",
     "gemm/gemm_mx4.hip",
+    "gemm/gemm_skinny.hip",
     "gemm/mx_quant.hip",
     "gemm/mx_quant_t.hip",
     "gemm/gemm_generic.hip",
@@ -68,10 +69,14 @@ SOURCES = [  # heaviest translation units first (the parallel build's critical p
     "runtime/plan.cpp",
     "bindings.cpp",
 ]
+# Per-source compiler flags. The skinny GEMM is built without the packed-f32 VALU instructions
+# (v_pk_add / mul / fma_f32): its epilogue and reduce arithmetic stays scalar f32.
+EXTRA_FLAGS = {"gemm/gemm_skinny.hip": ["-Xclang", "-target-feature", "-Xclang",
+                                        "-packed-fp32-ops"]}
 HEADERS = ["gemm/gemm.h", "gemm/gemm_kernels.h", "gemm/gemm_entry.h", "gemm/tile_map.h",
            "gemm/device_info.h", "gemm/mx_cvt.h", "gemm/mx_quant_in.h", "gemm/row_io.h",
            "gemm/glu_act.h", "gemm/gemm_grouped_kernels.h", "gemm/gemm_kgrouped_kernels.h",
-           "moe/moe.h", "moe/moe_route_map.h", "runtime/kernels.h", "comm/comm.h",
+           "gemm/gemm_skinny.h", "moe/moe.h", "moe/moe_route_map.h", "runtime/kernels.h", "comm/comm.h",
            "runtime/plan.h", "runtime/plan_ir.h"]
 
 
@@ -142,7 +147,7 @@ def _compile(src_rel: str, force: bool, verbose: bool):
     if not force and _stamp_ok(obj, digest):
         return obj, False
     cmd = [_hipcc(), "-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}",
-           "-Wno-unused-result", "-DNDEBUG"]
+           "-Wno-unused-result", "-DNDEBUG"] + EXTRA_FLAGS.get(src_rel, [])
     if src.endswith(".cpp"):
         cmd += ["-x", "hip"]  # host code that includes HIP headers; no device code inside
     cmd += [f"-I{d}" for d in _includes()] + ["-c", src, "-o", obj]

@@ -28,6 +28,14 @@ routes every token to ``top_k`` experts::
 
 ``top_k = 1`` with gates of 1 is the layer above, bit for bit. The default ``dispatch="torch"`` is
 the chain of torch ops at the top and knows only ``top_k = 1``.
+
+``kernel="skinny"`` (decode: few rows per expert) runs both layers on the weight-streaming
+``ops.gemm.gemm_skinny_grouped`` instead of the tiled grouped GEMM, with either dispatch::
+
+    C  = Xq W1[e].T                  f32 [T, 2F]
+    H  = glu(C)                      ops.glu.glu, f32
+    Hq, sH = quantise(H)             the row quantiser
+    Yp = Hq W2[e].T                  bf16
 """
 
 from __future__ import annotations
@@ -77,12 +85,13 @@ def expert_ids_topk(seq: int, experts: int, k: int, seed: int = 0):
 
 
 DISPATCHES = ("torch", "native")
+KERNELS = ("tiled", "skinny")
 
 
 class MxMoE:
     def __init__(self, hidden: int, ffn: int, seq: int, experts: int, fmt: str = "mx",
                  act: str = "silu", fused: bool = True, seed: int = 0, tile: str = "auto",
-                 top_k: int = 1, dispatch: str = "torch"):
+                 top_k: int = 1, dispatch: str = "torch", kernel: str = "tiled"):
         import torch
 
         from ddlb_amd.ops.gemm import ACTS, MAX_GROUPS, pack_glu_grouped
@@ -101,6 +110,8 @@ class MxMoE:
             raise ValueError("seq must be positive")
         if dispatch not in DISPATCHES:
             raise ValueError(f"dispatch must be one of {DISPATCHES}, not {dispatch!r}")
+        if kernel not in KERNELS:
+            raise ValueError(f"kernel must be one of {KERNELS}, not {kernel!r}")
         if isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 1:
             raise ValueError(f"top_k must be a positive int, not {top_k!r}")
         if top_k > 1 and dispatch != "native":
@@ -113,7 +124,7 @@ class MxMoE:
                                "(MxMoE.reference_chain runs anywhere)")
         self.H, self.F, self.S, self.E = hidden, ffn, seq, experts
         self.act, self.fmt, self.fused, self.tile = act, fmt, bool(fused), tile
-        self.top_k, self.dispatch = top_k, dispatch
+        self.top_k, self.dispatch, self.kernel = top_k, dispatch, kernel
         dev = torch.device("cuda", torch.cuda.current_device())
         g = torch.Generator(device=dev)
         g.manual_seed(seed)
@@ -174,15 +185,26 @@ class MxMoE:
         else:
             perm, offsets = self.route()
             xq, xs = quant(self.X.index_select(0, perm))
-        if self.fused:
+        if self.kernel == "skinny":
+            from ddlb_amd.ops.gemm import gemm_skinny_grouped
+            from ddlb_amd.ops.glu import glu
+
+            c = gemm_skinny_grouped(xq, self.w1q, offsets, a_scale=xs, w_scale=self.w1s,
+                                    out_dtype=torch.float32)
+            hq, hs = quant(glu(c, self.act))
+        elif self.fused:
             hq, hs = gemm_grouped(xq, self.w1q, offsets, a_scale=xs, w_scale=self.w1s,
                                   act=self.act, tile=self.tile, glu=True, out_quant=self.fmt)
         else:
             h = gemm_grouped(xq, self.w1q, offsets, a_scale=xs, w_scale=self.w1s, act=self.act,
                              tile=self.tile, glu=True, out_dtype=torch.bfloat16)
             hq, hs = quant(h)
-        gemm_grouped(hq, self.w2q, offsets, self.ysorted, a_scale=hs, w_scale=self.w2s,
-                     tile=self.tile)
+        if self.kernel == "skinny":
+            gemm_skinny_grouped(hq, self.w2q, offsets, self.ysorted, a_scale=hs,
+                                w_scale=self.w2s)
+        else:
+            gemm_grouped(hq, self.w2q, offsets, self.ysorted, a_scale=hs, w_scale=self.w2s,
+                         tile=self.tile)
         if native:
             combine(self.ysorted, slot_row, self.gates, out=self.out)
         else:

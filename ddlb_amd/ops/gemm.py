@@ -17,6 +17,9 @@ data and E8M0 scales per 32 output columns, quantised in the GEMM's epilogue.
 epilogue writes ``act(gate) * up``, half as many columns, dense or quantised.
 ``gemm_grouped(a, w, offsets)``: per-expert weights ``w [E, N, K]`` over contiguous runs of rows
 of ``a`` given by device-side int32 offsets, one launch, every form above on the tiled kernel.
+``gemm_skinny(a, w)`` / ``gemm_skinny_grouped(a, w, offsets)``: block-scaled fp8 / fp4 operands at
+decode shapes (``M`` or the rows per expert ``<= 64``) on the weight-streaming split-K kernel
+(``csrc/gemm/gemm_skinny.hip``); nothing above routes to it.
 """
 
 from __future__ import annotations
@@ -1012,3 +1015,187 @@ def gemm_kgrouped(a, w, offsets, rows, out=None, *, a_scale, w_scale, out_dtype=
             tile=TILES[tile], stream=s, a_scale=a_scale.data_ptr(), b_scale=w_scale.data_ptr(),
             a_scale_ld=a_scale.stride(0), b_scale_ld=w_scale.stride(0)),
         groups=E, stream=stream)
+
+
+# ---------------------------------------------------------------- skinny-M GEMM (decode shapes)
+SKINNY_NR = 2                    # gemm_skinny.h kSkinnyNR: 16-row W tiles per wave
+SKINNY_STRIP = 64 * SKINNY_NR    # W rows per workgroup (4 waves)
+SKINNY_MAX_SLICES = 16           # the cap of the automatic slice count
+
+
+def skinny_strips(N: int) -> int:
+    """Workgroups along N: strips of :data:`SKINNY_STRIP` weight rows, the last one ragged."""
+    return -(-int(N) // SKINNY_STRIP)
+
+
+def skinny_slices(nk: int, S: int):
+    """The K-tile ranges ``[k0, k1)`` of the ``S`` slices of ``nk`` K-tiles (gemm_skinny.h
+    ``skinny_slice``): contiguous, in order, none empty for ``S <= nk``."""
+    return [(s * nk // S, (s + 1) * nk // S) for s in range(S)]
+
+
+def skinny_auto_slices(strips: int, nk: int, groups: int = 1, cus: int = 0) -> int:
+    """The automatic slice count (gemm_skinny.h ``skinny_auto_slices``): the smallest
+    ``S <= min(nk, 16)`` whose grid ``strips * S * groups`` has two workgroups per CU, else that
+    cap."""
+    cus = cus or device_cus()
+    cap = min(int(nk), SKINNY_MAX_SLICES)
+    for S in range(1, cap):
+        if strips * S * groups >= 2 * cus:
+            return S
+    return cap
+
+
+def skinny_workspace_floats(S: int, rows: int, N: int) -> int:
+    """Floats of the partial-sum workspace ``[S, rows, N]``; none without a K-split."""
+    return S * rows * N if S > 1 else 0
+
+
+def _check_skinny(a, w, offsets=None, out=None, *, a_scale=None, w_scale=None, out_dtype=None,
+                  act: str = "none", ksplit="auto", workspace=None, grouped: bool = False):
+    """Every refusal of the skinny GEMMs, on the host and before anything is loaded or launched
+    (CPU tensors pass through it; the offsets' content is never read). Returns
+    ``(M, N, K, E, output dtype, S)``: ``K`` in elements, ``E = 0`` for the dense form, ``S`` the
+    number of K-slices."""
+    import torch
+
+    what = "the grouped skinny GEMM" if grouped else "the skinny GEMM"
+    if act not in ACTS:
+        raise ValueError(f"unknown activation {act!r}")
+    wd = 3 if grouped else 2
+    if not isinstance(a, torch.Tensor) or not isinstance(w, torch.Tensor) or a.dim() != 2 \
+            or w.dim() != wd:
+        raise ValueError(f"{what} takes a as [M, K] and w as "
+                         f"{'[E, N, K]' if grouped else '[N, K]'}, not "
+                         f"{tuple(getattr(a, 'shape', ()))} and {tuple(getattr(w, 'shape', ()))}")
+    fp4 = _is_fp4(a) or _is_fp4(w)
+    if not fp4 and a.dtype != torch.float8_e4m3fn and w.dtype != torch.float8_e4m3fn:
+        raise TypeError(f"{what} takes block-scaled fp8 or fp4 operands, not {a.dtype}")
+    _check_same_dtype(a, w)
+    if a_scale is None or w_scale is None:
+        raise ValueError(f"{what} needs a_scale and w_scale (there is no unit-scale kernel)")
+    if w.device != a.device:
+        raise ValueError("operands on different devices")
+    _check_k(a, w)
+    f = _MX_FP4 if fp4 else _MX_FP8
+    M, N, K = a.shape[0], w.shape[-2], f.per_byte * a.shape[1]
+    E = w.shape[0] if grouped else 0
+    if N < 1:
+        raise ValueError(f"{what} needs N >= 1")
+    _check_32_bits(M, N, K)
+    if grouped:
+        if not 1 <= E <= MAX_GROUPS:
+            raise ValueError(f"{what} takes 1 .. {MAX_GROUPS} groups, not {E}")
+        _check_offsets_dtype(offsets)
+        if offsets.dim() != 1 or offsets.shape[0] != E + 1 or not offsets.is_contiguous():
+            raise ValueError(f"offsets must be contiguous with shape ({E + 1},) for {E} groups, "
+                             f"not {tuple(offsets.shape)}")
+        if offsets.device != a.device:
+            raise ValueError(f"offsets is on {offsets.device}, the operands on {a.device}")
+        if E > 1 and w.stride(0) < N * w.stride(1):
+            raise ValueError(f"w needs experts at least N rows apart (strides "
+                             f"{tuple(w.stride())})")
+        if w.stride(0) * w.element_size() % 16:
+            raise ValueError("the experts' weights must be a multiple of 16 bytes apart")
+        if not isinstance(w_scale, torch.Tensor) or w_scale.dim() != 3:
+            raise ValueError(f"w_scale must have shape {(E, N, K // 32)}, not "
+                             f"{tuple(getattr(w_scale, 'shape', ()))}")
+        if w_scale.stride(0) % f.align or (E > 1 and w_scale.stride(0) < N * w_scale.stride(1)):
+            raise ValueError(f"w_scale needs experts a multiple of {f.align} bytes and at least "
+                             f"N rows apart (strides {tuple(w_scale.stride())})")
+    for name, t in (("a", a), ("w", w)):
+        if t.stride(-1) != 1 or t.stride(-2) < t.shape[-1]:
+            raise ValueError(f"{name} needs unit inner stride and rows of at least K (strides "
+                             f"{tuple(t.stride())})")
+        if t.data_ptr() % 16 or t.stride(-2) * t.element_size() % 16:
+            raise ValueError(f"{what} needs 16-byte-aligned rows of {name}")
+    # K modulus and the scale layout: the block-scaled formats' own rules, per expert slice
+    for g in sorted({0, E - 1}) if grouped else (None,):
+        _check_block_scaled(f, a, w if g is None else w[g], a_scale,
+                            w_scale if g is None else w_scale[g], M, "auto", "auto", 0, 0)
+    odt = _check_dense_out(what, a, out, out_dtype,
+                           (torch.bfloat16, torch.float16, torch.float32), M, N)
+    nk = K // f.kmod
+    if ksplit == "auto":
+        S = skinny_auto_slices(skinny_strips(N), nk, max(E, 1))
+    elif isinstance(ksplit, bool) or not isinstance(ksplit, int) or not 1 <= ksplit <= nk:
+        raise ValueError(f"ksplit must be 'auto' or an int in 1 .. {nk} (the K-tiles), not "
+                         f"{ksplit!r}")
+    else:
+        S = ksplit
+    if workspace is not None:
+        if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.float32:
+            raise TypeError(f"workspace must be a float32 tensor, not "
+                            f"{getattr(workspace, 'dtype', type(workspace))}")
+        if workspace.device != a.device:
+            raise ValueError(f"workspace is on {workspace.device}, the operands on {a.device}")
+        need = skinny_workspace_floats(S, M, N)
+        if not workspace.is_contiguous() or workspace.numel() < need or workspace.data_ptr() % 16:
+            raise ValueError(f"workspace must be contiguous, 16-byte aligned and hold at least "
+                             f"{need} floats ({S} slices x {M} x {N}), not {workspace.numel()}")
+    return M, N, K, E, odt, S
+
+
+def _run_skinny(t, a, w, offsets, out, a_scale, w_scale, act, workspace, stream):
+    """The launch of both skinny forms, after every refusal of :func:`_check_skinny` (``t``)."""
+    import torch
+
+    M, N, K, E, odt, S = t
+    C = load()
+    if a.device.type != "cuda":
+        raise ValueError("native GEMM operands must be ROCm device tensors")
+    if out is None:
+        out = torch.empty((M, N), dtype=odt, device=a.device)
+    if S > 1 and workspace is None:
+        workspace = torch.empty(skinny_workspace_floats(S, M, N), dtype=torch.float32,
+                                device=a.device)
+    am = 2 if _is_fp4(a) else 1
+    s = _stream(stream, a)
+    C.gemm_skinny(
+        a=a.data_ptr(), w=w.data_ptr(), c=out.data_ptr(), lda=am * a.stride(0),
+        ldw=am * w.stride(-2), ldc=out.stride(0), M=M, N=N, K=K,
+        din=DT_FP4 if am == 2 else DT_FP8, dout=dtype_code(odt), a_scale=a_scale.data_ptr(),
+        w_scale=w_scale.data_ptr(), a_scale_ld=a_scale.stride(0), w_scale_ld=w_scale.stride(-2),
+        act=ACTS[act], ksplit=S, ws=workspace.data_ptr() if S > 1 else 0,
+        offs=offsets.data_ptr() if E else 0, ngroups=E, w_gstride=am * w.stride(0) if E else 0,
+        w_scale_gstride=w_scale.stride(0) if E else 0, stream=s)
+    if stream is not None:  # what was allocated here stays allocated until that stream is done
+        out.record_stream(torch.cuda.ExternalStream(s))
+        if S > 1:
+            workspace.record_stream(torch.cuda.ExternalStream(s))
+    return out
+
+
+def gemm_skinny(a, w, out=None, *, a_scale, w_scale, out_dtype=None, act: str = "none",
+                ksplit="auto", workspace=None, stream=None):
+    """``out = act(a @ w.T)`` for decode shapes, ``M <= 64``, on the weight-streaming split-K
+    kernel (``csrc/gemm/gemm_skinny.hip``): block-scaled fp8 (``K % 128 == 0``) or MXFP4
+    (``K = 2 * a.shape[1]``, ``K % 256 == 0``) operands with ``a_scale [M, K / 32]`` and
+    ``w_scale [N, K / 32]`` as :func:`gemm` takes them, any ``N >= 1``, output bf16 (default) /
+    f16 / f32. The weights are read once for up to 64 rows and never staged through LDS; any
+    ``M`` is correct, but past 64 rows they are streamed once per 64 rows and :func:`gemm` is the
+    kernel to use.
+
+    ``ksplit``: the number of K-slices, ``"auto"`` (:func:`skinny_auto_slices`, which depends on
+    the device's CU count) or an int in ``1 .. nk`` K-tiles, which fixes the summation order on
+    every device. Slices write f32 partials into ``workspace`` (float32,
+    :func:`skinny_workspace_floats`; allocated here when absent) and a second kernel sums them in
+    slice order, applies ``act`` and rounds once: no atomics, two runs write the same bytes.
+    :func:`_check_skinny` holds every refusal."""
+    t = _check_skinny(a, w, None, out, a_scale=a_scale, w_scale=w_scale, out_dtype=out_dtype,
+                      act=act, ksplit=ksplit, workspace=workspace)
+    return _run_skinny(t, a, w, None, out, a_scale, w_scale, act, workspace, stream)
+
+
+def gemm_skinny_grouped(a, w, offsets, out=None, *, a_scale, w_scale, out_dtype=None,
+                        act: str = "none", ksplit="auto", workspace=None, stream=None):
+    """:func:`gemm_skinny` over per-expert weights in one launch, for few rows per expert
+    (``<= 64``; more are correct and slow): rows ``[o'[g], o'[g + 1])`` of ``a [T, K]`` times
+    ``w[g]`` of ``w [E, N, K]`` under ``w_scale [E, N, K / 32]``. ``offsets`` is the int32
+    ``[E + 1]`` device tensor of :func:`gemm_grouped`, read and clamped by the kernels only
+    (:func:`clamp_offsets`; no host sync). A group's rows are bit for bit what
+    :func:`gemm_skinny` writes for them with the same ``ksplit``; rows outside
+    ``[o'[0], o'[E])`` are not written. The workspace holds ``S * T * N`` floats."""
+    t = _check_skinny(a, w, offsets, out, a_scale=a_scale, w_scale=w_scale, out_dtype=out_dtype,
+                      act=act, ksplit=ksplit, workspace=workspace, grouped=True)
+    return _run_skinny(t, a, w, offsets, out, a_scale, w_scale, act, workspace, stream)

@@ -1,0 +1,200 @@
+"""Microbenchmark: the skinny-M GEMM beside the tiled kernel on the same block-scaled operands.
+
+In ONE process, alternating per shape: ``gemm_skinny`` against ``gemm`` (dense: M in 1, 4, 16, 64
+times (N, K) in (4096, 4096), (8192, 8192)) and ``gemm_skinny_grouped`` against ``gemm_grouped``
+(E = 32 experts, 8 and 64 tokens routed top-4, H = 4096, F = 1536: the fc1 and fc2 shapes), MX-fp8
+and MXFP4. Before anything is timed the two outputs are compared on the same seeded inputs
+(``atol = 1e-3 K``: both accumulate in f32, in different orders). Every shape is warmed; device
+events surround ``iters`` back-to-back calls; variants alternate over ``rounds`` rounds and the
+median, minimum and round-to-round spread are reported. Successive calls walk through copies of
+the weights that together exceed the 256 MB last-level cache, so the weights come from HBM.
+
+Printed per row: time per call, the weight-plus-scale bytes the shape needs (computed here from
+the shape; grouped: the experts that received rows), the bytes/s that gives, and its share of
+the HBM peak (8.0 TB/s, the MI355X specification).
+
+    python scripts/bench_skinny.py --json out/skinny.json
+"""
+
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+HBM_PEAK = 8.0e12         # bytes/s, specification
+ROTATE_BYTES = 512 << 20  # weight copies walked through: twice the last-level cache
+DENSE_MS = (1, 4, 16, 64)
+DENSE_NK = ((4096, 4096), (8192, 8192))
+MOE = dict(E=32, top_k=4, H=4096, F=1536, tokens=(8, 64))
+
+
+def timeit(fn, iters, warm):
+    import torch
+
+    for _ in range(warm):
+        fn()
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    s.record()
+    for _ in range(iters):
+        fn()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) / iters
+
+
+def summarise(ts):
+    med = statistics.median(ts)
+    return {"ms_median": med, "ms_min": min(ts), "ms_max": max(ts),
+            "spread": (max(ts) - min(ts)) / med}
+
+
+def weight_bytes(rows, K, fmt):
+    """Data plus scale bytes of ``rows`` weight rows of K elements."""
+    return rows * (K // (2 if fmt == "mxfp4" else 1) + K // 32)
+
+
+def _quant(shape, fmt, gen, scale=1.0):
+    import torch
+
+    from ddlb_amd.models.mx_mlp import _fmt_ops
+
+    x = torch.randn(shape, generator=gen, device=gen.device, dtype=torch.bfloat16) * scale
+    return _fmt_ops(fmt)[0](x)
+
+
+def _copies(q, s, nbytes):
+    """Enough copies of a weight and its scales to exceed ``ROTATE_BYTES`` (at most 64)."""
+    n = max(1, min(64, -(-ROTATE_BYTES // nbytes)))
+    return [(q, s)] + [(q.clone(), s.clone()) for _ in range(n - 1)]
+
+
+def _cycler(fn, sets):
+    state = [0]
+
+    def call():
+        state[0] = (state[0] + 1) % len(sets)
+        return fn(*sets[state[0]])
+    return call
+
+
+def _measure(variants, nbytes, iters, rounds):
+    """``variants``: name -> zero-argument call. Alternating rounds; bytes/s from the median."""
+    ts = {k: [] for k in variants}
+    for k, fn in variants.items():   # every shape and kernel warmed before the timed rounds
+        timeit(fn, 3, 3)
+    for _ in range(rounds):
+        for k, fn in variants.items():
+            ts[k].append(timeit(fn, iters, 2))
+    out = {k: summarise(v) for k, v in ts.items()}
+    for k in out:
+        out[k]["bytes_per_s"] = nbytes / (out[k]["ms_median"] * 1e-3)
+        out[k]["share_of_hbm_peak"] = out[k]["bytes_per_s"] / HBM_PEAK
+    out["skinny_over_tiled"] = out["skinny"]["ms_median"] / out["tiled"]["ms_median"]
+    return out
+
+
+def bench_dense(fmt, M, N, K, iters, rounds, gen):
+    import torch
+
+    from ddlb_amd.ops.gemm import gemm, gemm_skinny
+
+    a, sa = _quant((M, K), fmt, gen)
+    w, sw = _quant((N, K), fmt, gen, K ** -0.5)
+    nbytes = weight_bytes(N, K, fmt)
+    sets = _copies(w, sw, nbytes)
+    out_s = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
+    out_t = torch.empty_like(out_s)
+    skinny = lambda w, sw: gemm_skinny(a, w, out_s, a_scale=sa, w_scale=sw)       # noqa: E731
+    tiled = lambda w, sw: gemm(a, w, out_t, a_scale=sa, w_scale=sw)               # noqa: E731
+    skinny(w, sw), tiled(w, sw)
+    torch.cuda.synchronize()
+    torch.testing.assert_close(out_s.float(), out_t.float(), rtol=2.0 ** -7, atol=1e-3 * K)
+    r = _measure({"skinny": _cycler(skinny, sets), "tiled": _cycler(tiled, sets)}, nbytes, iters,
+                 rounds)
+    r.update(kind="dense", fmt=fmt, M=M, N=N, K=K, weight_bytes=nbytes, copies=len(sets))
+    return r
+
+
+def bench_grouped(fmt, tokens, N, K, layer, iters, rounds, gen):
+    import torch
+
+    from ddlb_amd.ops.gemm import gemm_grouped, gemm_skinny_grouped
+
+    E, T = MOE["E"], tokens * MOE["top_k"]
+    ids = torch.randint(0, E, (T,), generator=gen, device=gen.device)
+    counts = torch.bincount(ids, minlength=E)
+    offs = torch.zeros(E + 1, dtype=torch.int32, device=gen.device)
+    offs[1:] = torch.cumsum(counts, 0)
+    a, sa = _quant((T, K), fmt, gen)
+    w, sw = _quant((E * N, K), fmt, gen, K ** -0.5)
+    w, sw = w.reshape(E, N, -1), sw.reshape(E, N, -1)
+    nbytes = weight_bytes(int((counts > 0).sum()) * N, K, fmt)
+    sets = _copies(w, sw, weight_bytes(E * N, K, fmt))
+    out_s = torch.empty((T, N), dtype=torch.bfloat16, device=a.device)
+    out_t = torch.empty_like(out_s)
+    skinny = lambda w, sw: gemm_skinny_grouped(a, w, offs, out_s, a_scale=sa,      # noqa: E731
+                                               w_scale=sw)
+    tiled = lambda w, sw: gemm_grouped(a, w, offs, out_t, a_scale=sa, w_scale=sw)  # noqa: E731
+    skinny(w, sw), tiled(w, sw)
+    torch.cuda.synchronize()
+    torch.testing.assert_close(out_s.float(), out_t.float(), rtol=2.0 ** -7, atol=1e-3 * K)
+    r = _measure({"skinny": _cycler(skinny, sets), "tiled": _cycler(tiled, sets)}, nbytes, iters,
+                 rounds)
+    r.update(kind="grouped", layer=layer, fmt=fmt, tokens=tokens, T=T, E=E, N=N, K=K,
+             experts_with_rows=int((counts > 0).sum()), weight_bytes=nbytes, copies=len(sets))
+    return r
+
+
+def show(r):
+    what = (f"dense M={r['M']:<3d}" if r["kind"] == "dense"
+            else f"moe {r['layer']} tok={r['tokens']:<3d}")
+    line = f"{r['fmt']:6s} {what} N={r['N']:<5d} K={r['K']:<5d} {r['weight_bytes'] / 1e6:8.1f} MB"
+    for k in ("skinny", "tiled"):
+        v = r[k]
+        line += (f" | {k} {v['ms_median'] * 1e3:8.1f} us (min {v['ms_min'] * 1e3:.1f}, spread "
+                 f"{100 * v['spread']:.1f} %) {v['bytes_per_s'] / 1e12:5.2f} TB/s "
+                 f"{100 * v['share_of_hbm_peak']:5.1f} % of peak")
+    print(line + f" | skinny / tiled {r['skinny_over_tiled']:.3f}", flush=True)
+
+
+def main(argv=None):
+    import torch
+
+    p = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    p.add_argument("--iters", type=int, default=300)
+    p.add_argument("--rounds", type=int, default=5)
+    p.add_argument("--fmts", default="mx,mxfp4")
+    p.add_argument("--json", default="")
+    a = p.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_skinny.py measures on a ROCm GPU; none is visible")
+    from ddlb_amd.ops import gemm as G
+
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    rows = []
+    for fmt in a.fmts.split(","):
+        for N, K in DENSE_NK:
+            for M in DENSE_MS:
+                rows.append(bench_dense(fmt, M, N, K, a.iters, a.rounds, gen))
+                show(rows[-1])
+        for tokens in MOE["tokens"]:
+            for layer, N, K in (("fc1", 2 * MOE["F"], MOE["H"]), ("fc2", MOE["H"], MOE["F"])):
+                rows.append(bench_grouped(fmt, tokens, N, K, layer, a.iters, a.rounds, gen))
+                show(rows[-1])
+    res = {"device": torch.cuda.get_device_name(0), "cus": G.device_cus(), "nr": G.SKINNY_NR,
+           "iters": a.iters, "rounds": a.rounds, "hbm_peak": HBM_PEAK, "rows": rows}
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+    return res
+
+
+if __name__ == "__main__":
+    main()
