@@ -6,8 +6,10 @@
 // A workgroup is 4 waves, each owning kSkinnyNR 16-row tiles of W: a strip of 64 kSkinnyNR weight
 // rows. It walks one K-slice of its strip; the grid is strips x S x groups. S > 1 writes f32
 // partials [S, rows, N] that a second kernel sums in the order s = 0 .. S - 1 (no atomics: two
-// runs write the same bytes). Any M is correct; past 64 rows the weights are streamed once per
-// 64 rows, which is what the tiled kernel is for.
+// runs write the same bytes). The epilogue, at the unsplit store or in that second kernel, is
+// dense or gated (glu) and / or MX-quantising (c_scale): a decode FFN's fc1 in one call. Any M is
+// correct; past 64 rows the weights are streamed once per 64 rows, which is what the tiled kernel
+// is for.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -32,7 +34,7 @@ static_assert(kSkinnyNR == 1 || kSkinnyNR == 2, "one or two W tiles per wave");
 
 // Operand and scale layouts are GemmArgs' (gemm.h): leading dimensions in ELEMENTS (fp4: two per
 // byte), scale rows in BYTES, one E8M0 byte per 32 K elements. din DT_FP8 (K % 128 == 0) or DT_FP4
-// (K % 256 == 0); dout bf16 / f16 / f32. Operand rows 16-byte aligned; scale base and row stride
+// (K % 256 == 0); dout bf16 / f16 / f32 (c_scale: DT_FP8 / DT_FP4). Operand rows 16-byte aligned; scale base and row stride
 // multiples of 4 (fp4: 8). Any N >= 1; M == 0 launches nothing.
 struct SkinnyArgs {
   const void* a = nullptr;
@@ -55,6 +57,20 @@ struct SkinnyArgs {
   const int* offs = nullptr;
   int ngroups = 0;
   int64_t w_gstride = 0, w_scale_gstride = 0;
+  // Quantised output (optional; dout = DT_FP8 / DT_FP4 and only then), as GemmArgs::c_scale: the
+  // epilogue quantises its f32 result by the MX rule (mx_cvt.h) in 32-column blocks of a row and
+  // writes c as e4m3 bytes or E2M1 nibble pairs (ldc in ELEMENTS, even) with rows 16-byte
+  // aligned, and the blocks' E8M0 bytes here, rows c_scale_ld BYTES apart (base and stride
+  // multiples of 4; fp4 data: 8): the next GEMM's a and a_scale. Output columns % 128 == 0
+  // (fp4: 256).
+  uint8_t* c_scale = nullptr;
+  int64_t c_scale_ld = 0;
+  // Gated (GLU) epilogue (optional), as GemmArgs::glu: w is the [N, K] weight in the pack_glu
+  // layout (rows 64g .. 64g + 31 gate, 64g + 32 .. 64g + 63 the matching up rows), N % 64 == 0,
+  // and c has N / 2 columns: c[i, 32g + j] = act(sum[i, 64g + j]) * sum[i, 64g + 32 + j], one f32
+  // multiply, then rounded once to dout or quantised (c_scale: [M, N / 64]). ldc >= N / 2. N
+  // stays the rows of w: the strips, the slices and the workspace do not change.
+  int glu = 0;
 };
 hipError_t gemm_skinny_launch(const SkinnyArgs& p, int din, int dout, hipStream_t s);
 

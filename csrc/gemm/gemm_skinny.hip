@@ -20,22 +20,113 @@
 //   * MFMA operand order W, A: a lane holds 4 consecutive N-columns of one C row.
 //   * S == 1: the epilogue applies act, rounds once, stores C. S > 1: slice s stores f32 partials
 //     at ws[s], skinny_reduce_kernel sums them in the order 0 .. S - 1, applies act, rounds once.
+//   * The gated (SkinnyArgs::glu) and MX-quantising (SkinnyArgs::c_scale) epilogues sit at the
+//     same two sites: the unsplit kernel's final store and, for S > 1, skinny_epilogue_kernel in
+//     place of skinny_reduce_kernel (the partial kernel is the same). At both a lane owns four
+//     consecutive output columns and ends in skinny_store4; only the way a 32-column block's
+//     amax word is joined differs. Unsplit and gated, a wave's two W tiles are a gate tile and its
+//     up tile (the row map below), so the product is lane-local.
 // W rows >= N are clamped to row N - 1 for the loads and dropped at the store; nothing reads
 // outside a view; every row address is 64-bit. Non-finite values: the rule of gemm.h.
 #include "gemm_skinny.h"
 
 #include "gemm_kernels.h"
+#include "row_io.h"
 
 namespace ddlb {
 namespace {
 
 constexpr int PK = kSkinnyPanel, NR = kSkinnyNR, SNT = 64 * kSkinnyWaves;
 
+// ---------------------------------------------------------------- the epilogue tail
+// The output kind is one compile-time pair: OUT (bf16 / f16 / f32 dense, DT_FP8 / DT_FP4 quantised
+// by the rule of mx_cvt.h) and GLU. A lane holds four consecutive output columns of one row.
+template <int OUT> constexpr bool skinny_qout() { return OUT == DT_FP8 || OUT == DT_FP4; }
+template <int OUT> constexpr int skinny_bytes4() {  // bytes of four output columns
+  return OUT == DT_F32 ? 16 : OUT == DT_FP8 ? 4 : OUT == DT_FP4 ? 2 : 8;
+}
+
+// act(gate) * up: one f32 multiply, materialised before any conversion (row_io.h row_keep_f32)
+__device__ __forceinline__ f32x4 skinny_gate(const f32x4 g, const f32x4 u, int act) {
+  const f32x4 a = act4(g, act);
+  return f32x4{row_keep_f32(a.x * u.x), row_keep_f32(a.y * u.y), row_keep_f32(a.z * u.z),
+               row_keep_f32(a.w * u.w)};
+}
+
+// the four values' contribution to their block's amax word (dense outputs carry none)
+template <int OUT>
+__device__ __forceinline__ unsigned skinny_amax4(unsigned m, const f32x4 v) {
+  if constexpr (skinny_qout<OUT>()) {
+    constexpr bool Q4 = OUT == DT_FP4;
+    m = mx_amax_join<Q4>(m, mx_amax_bits<Q4>(v.x));
+    m = mx_amax_join<Q4>(m, mx_amax_bits<Q4>(v.y));
+    m = mx_amax_join<Q4>(m, mx_amax_bits<Q4>(v.z));
+    m = mx_amax_join<Q4>(m, mx_amax_bits<Q4>(v.w));
+  }
+  return m;
+}
+template <int OUT>
+__device__ __forceinline__ unsigned skinny_amax_xor(unsigned m, int d) {
+  if constexpr (skinny_qout<OUT>())
+    m = mx_amax_join<OUT == DT_FP4>(m, (unsigned)__shfl_xor((int)m, d));
+  return m;
+}
+
+// Four f32 values and their block's amax word -> one dword of e4m3, two bytes of E2M1, or a dense
+// Store4 at dst; the block's scale byte at sdst from the one lane that is given it.
+template <int OUT>
+__device__ __forceinline__ void skinny_tail(char* dst, uint8_t* sdst, const f32x4 v, unsigned m) {
+  if constexpr (skinny_qout<OUT>()) {
+    constexpr bool Q4 = OUT == DT_FP4;
+    const int e = mx_scale_exp<Q4>(m);
+    if constexpr (Q4) {
+      const float sc = mx_fp4_scale(e);
+      unsigned w = mx_cvt2_e2m1<0>(0u, v.x, v.y, sc);
+      w = mx_cvt2_e2m1<1>(w, v.z, v.w, sc);
+      *(unsigned short*)dst = (unsigned short)w;
+    } else {
+      *(unsigned*)dst = mx_cvt4_e4m3(v.x, v.y, v.z, v.w, e);
+    }
+    if (sdst != nullptr) *sdst = (uint8_t)mx_scale_byte<Q4>(m, e);
+  } else {
+    Store4<OUT>::st(dst, v);
+  }
+}
+
+// Columns col .. col + 3 of the row at crow, of ncols: the tail, or (dense rows that are ragged
+// or not aligned for the vector store) element by element. A quantised row holds whole blocks.
+template <int OUT>
+__device__ __forceinline__ void skinny_store4(char* crow, int64_t col, int64_t ncols, bool vec,
+                                              uint8_t* sdst, const f32x4 v4, unsigned m) {
+  constexpr int B4 = skinny_bytes4<OUT>();
+  if (col + 3 < ncols && (skinny_qout<OUT>() || vec)) {
+    skinny_tail<OUT>(crow + (col >> 2) * B4, sdst, v4, m);
+  } else if constexpr (!skinny_qout<OUT>()) {
+    const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+    for (int r = 0; r < 4; ++r)
+      if (col + r < ncols) Store4<OUT>::st1(crow + (col + r) * (B4 / 4), v[r]);
+  }
+}
+// whether a dense output's rows take the vector store
+template <int OUT>
+__device__ __forceinline__ bool skinny_vec(const SkinnyArgs& p) {
+  constexpr int B4 = skinny_bytes4<OUT>();
+  return ((((uintptr_t)p.c | (uint64_t)(p.ldc * (B4 / 4))) & (B4 - 1)) == 0);
+}
+
 // p arrives as the byte view gemm_skinny_launch forms (fp4: K, lda, ldw, w_gstride in bytes).
 // PART: the f32 partial of slice blockIdx.y, no activation; otherwise the whole K and the final
-// store in OUT.
-template <bool F4, int OUT, int MC, bool PART>
+// store: OUT dense or quantised, GLU gated.
+// W rows. Tile j of wave w is rows 128 strip + 32 w + 16 j + fr. GLU (unsplit only): rows
+// 128 strip + 64 (w >> 1) + 32 j + 16 (w & 1) + fr, the gate tile (j = 0) and its up tile of
+// output columns 64 strip + 32 (w >> 1) + 16 (w & 1) + 4 fq .. + 3: waves w, w ^ 1 share a block.
+template <bool F4, int OUT, int MC, bool PART, bool GLU = false>
 __global__ __launch_bounds__(SNT) void gemm_skinny_kernel(const SkinnyArgs p) {
+  static_assert(!PART || (OUT == DT_F32 && !GLU), "partials: f32 in W-row order");
+  static_assert(!(GLU || skinny_qout<OUT>()) || NR == 2, "a wave's two tiles: a pair, or a block");
+  static_assert(!(GLU && skinny_qout<OUT>()) || PK * (F4 ? 2 : 1) >= kSkinnyWaves,
+                "Ss holds an amax word per wave and row");
+  constexpr int TJ = GLU ? 32 : 16;         // W rows from tile j to tile j + 1
   constexpr int ROWS = 16 * MC;             // A rows per super-chunk
   constexpr int NA = ROWS * PK * 8 / SNT;   // 16-byte chunks of an A panel per thread
   constexpr int NS = (ROWS * PK + SNT - 1) / SNT;  // scale rows of a panel per thread
@@ -54,12 +145,13 @@ __global__ __launch_bounds__(SNT) void gemm_skinny_kernel(const SkinnyArgs p) {
   skinny_slice(p.K / 128, (int)gridDim.y, (int)blockIdx.y, kt0, kt1);
 
   // this lane's W rows (one per tile), at its first chunk, and their scale rows
-  const int n0 = blockIdx.x * kSkinnyStrip + wave * 16 * NR;
+  const int n0 = blockIdx.x * kSkinnyStrip +
+                 (GLU ? 64 * (wave >> 1) + 16 * (wave & 1) : wave * 16 * NR);
   const GLB_AS char* wp[NR];
   const GLB_AS char* wsp[NR];
 #pragma unroll
   for (int j = 0; j < NR; ++j) {
-    int64_t n = (int64_t)n0 + j * 16 + fr;
+    int64_t n = (int64_t)n0 + j * TJ + fr;
     n = n < p.N ? n : p.N - 1;
     wp[j] = (const GLB_AS char*)p.w + (int64_t)g * p.w_gstride + n * p.ldw + fq * 16;
     wsp[j] = (const GLB_AS char*)p.w_scale + (int64_t)g * p.w_scale_gstride + n * p.w_scale_ld;
@@ -197,28 +289,56 @@ __global__ __launch_bounds__(SNT) void gemm_skinny_kernel(const SkinnyArgs p) {
       }
     }
 
-    // a lane holds C[m0 + 16 i + fr][n0 + 16 j + 4 fq + 0 .. 3]
-    constexpr int OSZ = PART ? 4 : out_size<OUT>();
-    const bool vec = PART ? (p.N & 3) == 0
-                          : ((((uintptr_t)p.c | (uint64_t)(p.ldc * OSZ)) & (4 * OSZ - 1)) == 0);
+    // a lane holds C[m0 + 16 i + fr][n0 + TJ j + 4 fq + 0 .. 3]; gated: one quad of the N / 2
+    // output columns from its two tiles
+    constexpr int EO = PART ? DT_F32 : OUT;
+    constexpr int B4 = skinny_bytes4<EO>();
+    constexpr int NV = GLU ? 1 : NR;  // quads per lane and row
+    const int64_t ncols = GLU ? p.N / 2 : p.N;
+    const int64_t col0 = (GLU ? (int64_t)blockIdx.x * (kSkinnyStrip / 2) + 32 * (wave >> 1) +
+                                    16 * (wave & 1) : (int64_t)n0) + fq * 4;
+    const bool vec = PART ? (p.N & 3) == 0 : skinny_vec<EO>(p);
+    f32x4 v[MC][NV];
+    unsigned am[MC];
+#pragma unroll
+    for (int i = 0; i < MC; ++i) {
+      am[i] = 0;
+      if constexpr (GLU) {
+        v[i][0] = skinny_gate(acc[i][0], acc[i][1], p.act);
+      } else {
+#pragma unroll
+        for (int j = 0; j < NR; ++j) v[i][j] = PART ? acc[i][j] : act4(acc[i][j], p.act);
+      }
+      // the row's block: the wave's 32 columns (gated: its 16), over the four fq lanes
+#pragma unroll
+      for (int j = 0; j < NV; ++j) am[i] = skinny_amax4<EO>(am[i], v[i][j]);
+      am[i] = skinny_amax_xor<EO>(skinny_amax_xor<EO>(am[i], 16), 32);
+    }
+    if constexpr (GLU && skinny_qout<EO>()) {
+      // the other half of the block is wave ^ 1's: the words change hands through Ss, which
+      // every wave is done with behind the first barrier (all waves get here: rows past the
+      // range are dropped at the stores)
+      __syncthreads();
+#pragma unroll
+      for (int i = 0; i < MC; ++i) Ss[wave * ROWS + i * 16 + fr] = am[i];
+      __syncthreads();
+#pragma unroll
+      for (int i = 0; i < MC; ++i)
+        am[i] = mx_amax_join<EO == DT_FP4>(am[i], Ss[(wave ^ 1) * ROWS + i * 16 + fr]);
+    }
 #pragma unroll
     for (int i = 0; i < MC; ++i) {
       const int64_t row = (int64_t)m0 + i * 16 + fr;
       if (row >= r1) continue;
       char* crow = PART ? (char*)(p.ws + ((int64_t)blockIdx.y * p.M + row) * p.N)
-                        : (char*)p.c + row * p.ldc * OSZ;
+                        : (char*)p.c + row * p.ldc * B4 / 4;
+      uint8_t* sdst = nullptr;  // the scale byte: one lane per (row, block)
+      if constexpr (skinny_qout<EO>())
+        if (fq == 0 && !(GLU && (wave & 1))) sdst = p.c_scale + row * p.c_scale_ld + (col0 >> 5);
 #pragma unroll
-      for (int j = 0; j < NR; ++j) {
-        const int64_t col = (int64_t)n0 + j * 16 + fq * 4;
-        const f32x4 v4 = PART ? acc[i][j] : act4(acc[i][j], p.act);
-        if (col + 3 < p.N && vec) {
-          Store4<PART ? DT_F32 : OUT>::st(crow + col * OSZ, v4);
-        } else {
-          const float v[4] = {v4.x, v4.y, v4.z, v4.w};
-          for (int r = 0; r < 4; ++r)
-            if (col + r < p.N) Store4<PART ? DT_F32 : OUT>::st1(crow + (col + r) * OSZ, v[r]);
-        }
-      }
+      for (int j = 0; j < NV; ++j)
+        skinny_store4<EO>(crow, col0 + j * 16, ncols, vec, j == 0 ? sdst : nullptr, v[i][j],
+                          am[i]);
     }
   }
 }
@@ -241,23 +361,99 @@ __global__ __launch_bounds__(256) void skinny_reduce_kernel(const SkinnyArgs p, 
   Store4<OUT>::st1((char*)p.c + (row * p.ldc + col) * OSZ, act1(acc, p.act));
 }
 
+// The gated and / or quantising form of the reduce: a lane sums four consecutive columns of the
+// S slices in the same order (gated: the gate quad at 64 g + 4 t and the up quad at
+// 64 g + 32 + 4 t of output columns 32 g + 4 t ..), eight adjacent lanes are one 32-column block
+// (three cross-lane steps join its amax word), each lane stores its own quad and lane t = 0 the
+// scale byte. Rows of whole blocks (N % 64 == 0 at least), so a row is ncols / 4 quads, a
+// multiple of 8, and a block never straddles rows or the range's end. Grouped: as above.
+template <int OUT, bool GLU>
+__global__ __launch_bounds__(256) void skinny_epilogue_kernel(const SkinnyArgs p, const int S) {
+  int r0 = 0, r1 = p.M;
+  if (p.offs != nullptr) skinny_group_rows(p.offs, p.M, -1, p.ngroups, r0, r1);
+  const int64_t ncols = GLU ? p.N / 2 : p.N;
+  const int qpr = (int)(ncols / 4);
+  const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t row = (int64_t)r0 + q / qpr;
+  const int t4 = (int)(q % qpr);
+  const bool ok = row < r1;  // the same for the eight lanes of a block
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if (ok) {
+    const GLB_AS float* src = (const GLB_AS float*)p.ws + row * p.N +
+                              (GLU ? 64 * (t4 >> 3) + 4 * (t4 & 7) : 4 * t4);
+    const int64_t step = (int64_t)p.M * p.N;
+    f32x4 g = *(const GLB_AS f32x4*)src;
+#pragma unroll 4
+    for (int s = 1; s < S; ++s) g += *(const GLB_AS f32x4*)(src + s * step);
+    if constexpr (GLU) {
+      f32x4 u = *(const GLB_AS f32x4*)(src + 32);
+#pragma unroll 4
+      for (int s = 1; s < S; ++s) u += *(const GLB_AS f32x4*)(src + 32 + s * step);
+      v = skinny_gate(g, u, p.act);
+    } else {
+      v = act4(g, p.act);
+    }
+  }
+  unsigned m = skinny_amax4<OUT>(0u, v);
+#pragma unroll
+  for (int d = 1; d <= 4; d *= 2) m = skinny_amax_xor<OUT>(m, d);
+  if (!ok) return;
+  uint8_t* sdst = nullptr;
+  if constexpr (skinny_qout<OUT>())
+    if ((t4 & 7) == 0) sdst = p.c_scale + row * p.c_scale_ld + (t4 >> 3);
+  skinny_store4<OUT>((char*)p.c + row * p.ldc * skinny_bytes4<OUT>() / 4, 4 * (int64_t)t4, ncols,
+                     skinny_vec<OUT>(p), sdst, v, m);
+}
+
+// dout over the dense and the quantised outputs
+template <class F>
+hipError_t skinny_dispatch_out(int dout, F&& f) {
+  if (dout == DT_FP8) return f(std::integral_constant<int, DT_FP8>{});
+  if (dout == DT_FP4) return f(std::integral_constant<int, DT_FP4>{});
+  return dispatch_out(dout, f);
+}
+
 template <bool F4, int MC>
 hipError_t launch_skinny(const SkinnyArgs& p, int dout, int S, int groups, hipStream_t s) {
   const dim3 grid((unsigned)skinny_strips(p.N), (unsigned)S, (unsigned)groups), block(SNT);
+  const bool fused = p.glu != 0 || dout == DT_FP8 || dout == DT_FP4;
   if (S > 1) {
     hipLaunchKernelGGL((gemm_skinny_kernel<F4, DT_F32, MC, true>), grid, block, 0, s, p);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    const dim3 rgrid((unsigned)p.M, (unsigned)((p.N + 255) / 256));
+    if (!fused) {
+      const dim3 rgrid((unsigned)p.M, (unsigned)((p.N + 255) / 256));
+      return dispatch_out(dout, [&](auto o) {
+        hipLaunchKernelGGL((skinny_reduce_kernel<decltype(o)::value>), rgrid, dim3(256), 0, s, p,
+                           S);
+        return hipGetLastError();
+      });
+    }
+  }
+  if (!fused)
     return dispatch_out(dout, [&](auto o) {
-      hipLaunchKernelGGL((skinny_reduce_kernel<decltype(o)::value>), rgrid, dim3(256), 0, s, p, S);
+      hipLaunchKernelGGL((gemm_skinny_kernel<F4, decltype(o)::value, MC, false>), grid, block, 0,
+                         s, p);
       return hipGetLastError();
     });
+  if constexpr (NR == 2) {  // (a wave's two tiles are what the fused epilogues pair up)
+    const int64_t quads = (int64_t)p.M * ((p.glu ? p.N / 2 : p.N) / 4);
+    const dim3 egrid((unsigned)((quads + 255) / 256));
+    return skinny_dispatch_out(dout, [&](auto o) {
+      constexpr int O = decltype(o)::value;
+      auto go = [&](auto glu) {
+        constexpr bool G = decltype(glu)::value;
+        if constexpr (G || skinny_qout<O>()) {
+          if (S > 1)
+            hipLaunchKernelGGL((skinny_epilogue_kernel<O, G>), egrid, dim3(256), 0, s, p, S);
+          else
+            hipLaunchKernelGGL((gemm_skinny_kernel<F4, O, MC, false, G>), grid, block, 0, s, p);
+        }
+        return hipGetLastError();
+      };
+      return p.glu ? go(std::true_type{}) : go(std::false_type{});
+    });
   }
-  return dispatch_out(dout, [&](auto o) {
-    hipLaunchKernelGGL((gemm_skinny_kernel<F4, decltype(o)::value, MC, false>), grid, block, 0, s,
-                       p);
-    return hipGetLastError();
-  });
+  return hipErrorInvalidValue;
 }
 
 }  // namespace
@@ -267,12 +463,26 @@ hipError_t launch_skinny(const SkinnyArgs& p, int dout, int S, int groups, hipSt
 hipError_t gemm_skinny_launch(const SkinnyArgs& p_in, int din, int dout, hipStream_t s) {
   const bool f4 = din == DT_FP4;
   if (din != DT_FP8 && !f4) return hipErrorInvalidValue;
-  if (dout != DT_BF16 && dout != DT_F16 && dout != DT_F32) return hipErrorInvalidValue;
+  const bool q4 = dout == DT_FP4, qout = dout == DT_FP8 || q4;
+  if (dout != DT_BF16 && dout != DT_F16 && dout != DT_F32 && !qout) return hipErrorInvalidValue;
   SkinnyArgs p = p_in;
   if (p.M < 0 || p.N < 1 || p.K < 1 || p.K % (f4 ? 256 : 128)) return hipErrorInvalidValue;
   if (p.act < ACT_NONE || p.act > ACT_SILU) return hipErrorInvalidValue;
   if (!p.a || !p.w || !p.c || !p.a_scale || !p.w_scale) return hipErrorInvalidValue;
-  if (p.lda < p.K || p.ldw < p.K || p.ldc < p.N) return hipErrorInvalidValue;
+  // the output: N columns, gated N / 2 from whole 64-row gate / up groups; quantised with its
+  // scales and only then, in whole blocks as the GEMM that reads them takes per K-tile, rows
+  // and scale words aligned as that GEMM's a and a_scale (above)
+  const int64_t cols = p.glu ? p.N / 2 : p.N;
+  if ((p.glu && p.N % 64) || qout != (p.c_scale != nullptr)) return hipErrorInvalidValue;
+  if (p.lda < p.K || p.ldw < p.K || p.ldc < cols) return hipErrorInvalidValue;
+  if (qout) {
+    const int cal = q4 ? 8 : 4;
+    if (cols % (q4 ? 256 : 128) || (q4 && (p.ldc & 1))) return hipErrorInvalidValue;
+    if ((((uintptr_t)p.c | (uint64_t)(q4 ? p.ldc / 2 : p.ldc)) & 15) ||
+        (((uintptr_t)p.c_scale | (uint64_t)p.c_scale_ld) & (cal - 1)) ||
+        p.c_scale_ld < cols / 32 || (int64_t)p.M * p.c_scale_ld >= (int64_t(1) << 31))
+      return hipErrorInvalidValue;
+  }
   const bool grouped = p.offs != nullptr || p.ngroups != 0;
   if (grouped && (!p.offs || p.ngroups < 1 || p.ngroups > kMaxGroups)) return hipErrorInvalidValue;
   if (!grouped) p.w_gstride = p.w_scale_gstride = 0;

@@ -15,6 +15,11 @@ is ``[2F, H]`` (gate and up rows interleaved in groups of 32, quantised once lik
 fc1 runs with ``glu=True``, so the product is formed in the GEMM's epilogue and ``h`` is still
 ``[S, F]``; fused or not as above.
 
+``kernel="skinny"`` (decode: ``seq <= 64``) runs both layers on the weight-streaming
+``ops.gemm.gemm_skinny`` instead of the tiled kernel: fc1 with the quantised output, gated or
+``act`` only, straight into fc2. ``fused=False`` there is the chain the fused epilogue replaces
+(gated: f32 fc1, ``ops.glu.glu``, the row quantiser; else bf16 fc1 and the row quantiser).
+
 ``reference()`` is the torch chain on the dequantised operands in fp32:
 ``dequantize(quantize_reference(act(Xd @ W1d.T))) @ W2d.T`` (gated: ``glu_reference`` of the
 ``[S, 2F]`` product in place of ``act``).
@@ -23,6 +28,8 @@ fc1 runs with ``glu=True``, so the product is formed in the GEMM's epilogue and 
 from __future__ import annotations
 
 FMTS = ("mx", "mxfp4")
+KERNELS = ("tiled", "skinny")
+SKINNY_ROWS = 64  # the rows one pass over the weights serves (gemm_skinny)
 
 
 def _fmt_ops(fmt: str):
@@ -41,7 +48,7 @@ class MxMLP:
 
     def __init__(self, hidden: int, ffn: int, seq: int, dtype: str = "bfloat16",
                  act: str = "gelu", fmt: str = "mx", fused: bool = True, tile: str = "auto",
-                 seed: int = 0, gated: bool = False):
+                 seed: int = 0, gated: bool = False, kernel: str = "tiled"):
         import torch
 
         from ddlb_amd.ops.gemm import ACTS, pack_glu
@@ -58,12 +65,17 @@ class MxMLP:
                              f"(hidden = {hidden}, ffn = {ffn})")
         if seq <= 0:
             raise ValueError("seq must be positive")
+        if kernel not in KERNELS:
+            raise ValueError(f"kernel must be one of {KERNELS}, not {kernel!r}")
+        if kernel == "skinny" and seq > SKINNY_ROWS:
+            raise ValueError(f"kernel='skinny' is for seq <= {SKINNY_ROWS}, not {seq}: past that "
+                             "the tiled kernel is the one to use")
         if not torch.cuda.is_available():
             raise RuntimeError("MxMLP runs the native block-scaled GEMMs: it needs a ROCm GPU "
                                "(MxMLP.reference_chain runs anywhere)")
         self.H, self.F, self.S = hidden, ffn, seq
         self.dtype, self.act, self.fmt, self.fused, self.tile = dtype, act, fmt, bool(fused), tile
-        self.gated = bool(gated)
+        self.gated, self.kernel = bool(gated), kernel
         dev = torch.device("cuda", torch.cuda.current_device())
         g = torch.Generator(device=dev)
         g.manual_seed(seed)
@@ -93,6 +105,8 @@ class MxMLP:
         quant, _, _ = _fmt_ops(self.fmt)
         xq, xs = quant(self.X)
         glu = {"glu": True} if self.gated else {}
+        if self.kernel == "skinny":
+            return self._forward_skinny(xq, xs)
         if self.fused:
             hq, hs = gemm(xq, self.w1q, a_scale=xs, w_scale=self.w1s, act=self.act,
                           tile=self.tile, out_quant=self.fmt, **glu)
@@ -101,6 +115,26 @@ class MxMLP:
                      out_dtype=torch.bfloat16, **glu)
             hq, hs = quant(h)
         gemm(hq, self.w2q, self.out, a_scale=hs, w_scale=self.w2s, tile=self.tile)
+        return self.out
+
+    def _forward_skinny(self, xq, xs):
+        import torch
+
+        from ddlb_amd.ops.gemm import gemm_skinny
+
+        quant, _, _ = _fmt_ops(self.fmt)
+        fc1 = dict(a_scale=xs, w_scale=self.w1s)
+        if self.fused:
+            hq, hs = gemm_skinny(xq, self.w1q, act=self.act, glu=self.gated, out_quant=self.fmt,
+                                 **fc1)
+        elif self.gated:
+            from ddlb_amd.ops.glu import glu
+
+            hq, hs = quant(glu(gemm_skinny(xq, self.w1q, out_dtype=torch.float32, **fc1),
+                               self.act))
+        else:
+            hq, hs = quant(gemm_skinny(xq, self.w1q, act=self.act, **fc1))
+        gemm_skinny(hq, self.w2q, self.out, a_scale=hs, w_scale=self.w2s)
         return self.out
 
     @staticmethod

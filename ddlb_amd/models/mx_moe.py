@@ -30,7 +30,9 @@ routes every token to ``top_k`` experts::
 the chain of torch ops at the top and knows only ``top_k = 1``.
 
 ``kernel="skinny"`` (decode: few rows per expert) runs both layers on the weight-streaming
-``ops.gemm.gemm_skinny_grouped`` instead of the tiled grouped GEMM, with either dispatch::
+``ops.gemm.gemm_skinny_grouped`` instead of the tiled grouped GEMM, with either dispatch. With
+``fused=True`` fc1 is one call, ``gemm_skinny_grouped(..., glu=True, out_quant=fmt)``, and nothing
+goes between it and fc2; ``fused=False`` is the chain the fused epilogue replaces, the same bytes::
 
     C  = Xq W1[e].T                  f32 [T, 2F]
     H  = glu(C)                      ops.glu.glu, f32
@@ -185,7 +187,12 @@ class MxMoE:
         else:
             perm, offsets = self.route()
             xq, xs = quant(self.X.index_select(0, perm))
-        if self.kernel == "skinny":
+        if self.kernel == "skinny" and self.fused:
+            from ddlb_amd.ops.gemm import gemm_skinny_grouped
+
+            hq, hs = gemm_skinny_grouped(xq, self.w1q, offsets, a_scale=xs, w_scale=self.w1s,
+                                         act=self.act, glu=True, out_quant=self.fmt)
+        elif self.kernel == "skinny":
             from ddlb_amd.ops.gemm import gemm_skinny_grouped
             from ddlb_amd.ops.glu import glu
 

@@ -1052,16 +1052,21 @@ def skinny_workspace_floats(S: int, rows: int, N: int) -> int:
 
 
 def _check_skinny(a, w, offsets=None, out=None, *, a_scale=None, w_scale=None, out_dtype=None,
-                  act: str = "none", ksplit="auto", workspace=None, grouped: bool = False):
+                  act: str = "none", ksplit="auto", workspace=None, grouped: bool = False,
+                  glu: bool = False, out_quant=None, out_scale=None):
     """Every refusal of the skinny GEMMs, on the host and before anything is loaded or launched
     (CPU tensors pass through it; the offsets' content is never read). Returns
-    ``(M, N, K, E, output dtype, S)``: ``K`` in elements, ``E = 0`` for the dense form, ``S`` the
-    number of K-slices."""
+    ``(M, N, K, E, output dtype, S)``: ``K`` in elements, ``N`` the rows of ``w`` (the output has
+    ``N / 2`` columns with ``glu``), ``E = 0`` for the dense form, ``S`` the number of K-slices;
+    with ``out_quant`` the output dtype is the quantised data's."""
     import torch
 
     what = "the grouped skinny GEMM" if grouped else "the skinny GEMM"
     if act not in ACTS:
         raise ValueError(f"unknown activation {act!r}")
+    _known_out_quant(out_quant, optional=True)
+    if out_quant is None and out_scale is not None:
+        raise ValueError("out_scale goes with out_quant")
     wd = 3 if grouped else 2
     if not isinstance(a, torch.Tensor) or not isinstance(w, torch.Tensor) or a.dim() != 2 \
             or w.dim() != wd:
@@ -1113,8 +1118,20 @@ def _check_skinny(a, w, offsets=None, out=None, *, a_scale=None, w_scale=None, o
     for g in sorted({0, E - 1}) if grouped else (None,):
         _check_block_scaled(f, a, w if g is None else w[g], a_scale,
                             w_scale if g is None else w_scale[g], M, "auto", "auto", 0, 0)
-    odt = _check_dense_out(what, a, out, out_dtype,
-                           (torch.bfloat16, torch.float16, torch.float32), M, N)
+    # the output: N columns, or N / 2 from whole 64-row gate / up groups; quantised in whole
+    # 32-column blocks, as many as the GEMM that reads them takes per K-tile
+    cols = N // 2 if glu else N
+    nmod = (2 if glu else 1) * (256 if out_quant == "mxfp4" else 128 if out_quant else GLU_GROUP)
+    if (glu or out_quant) and N % nmod:
+        raise ValueError(f"{what} with glu={bool(glu)}, out_quant={out_quant!r} needs "
+                         f"N % {nmod} == 0 (N = {N})")
+    if out_quant is None:
+        odt = _check_dense_out(what, a, out, out_dtype,
+                               (torch.bfloat16, torch.float16, torch.float32), M, cols)
+    else:
+        _check_quant_dtype(out_quant, out_dtype)
+        _check_quant_outputs(a, out, out_scale, out_quant, M, cols)
+        odt = out_quant_dtype(out_quant)
     nk = K // f.kmod
     if ksplit == "auto":
         S = skinny_auto_slices(skinny_strips(N), nk, max(E, 1))
@@ -1136,7 +1153,8 @@ def _check_skinny(a, w, offsets=None, out=None, *, a_scale=None, w_scale=None, o
     return M, N, K, E, odt, S
 
 
-def _run_skinny(t, a, w, offsets, out, a_scale, w_scale, act, workspace, stream):
+def _run_skinny(t, a, w, offsets, out, a_scale, w_scale, act, workspace, stream, glu=False,
+                out_quant=None, out_scale=None):
     """The launch of both skinny forms, after every refusal of :func:`_check_skinny` (``t``)."""
     import torch
 
@@ -1144,30 +1162,42 @@ def _run_skinny(t, a, w, offsets, out, a_scale, w_scale, act, workspace, stream)
     C = load()
     if a.device.type != "cuda":
         raise ValueError("native GEMM operands must be ROCm device tensors")
-    if out is None:
-        out = torch.empty((M, N), dtype=odt, device=a.device)
+    cols = N // 2 if glu else N
+    if out is None and out_quant is not None:
+        out = torch.empty((M, cols // 2 if out_quant == "mxfp4" else cols), dtype=torch.uint8,
+                          device=a.device).view(odt)
+    elif out is None:
+        out = torch.empty((M, cols), dtype=odt, device=a.device)
+    if out_quant is not None and out_scale is None:
+        out_scale = torch.empty((M, cols // 32), dtype=torch.uint8, device=a.device)
     if S > 1 and workspace is None:
         workspace = torch.empty(skinny_workspace_floats(S, M, N), dtype=torch.float32,
                                 device=a.device)
-    am = 2 if _is_fp4(a) else 1
+    am, cm = (2 if _is_fp4(a) else 1), (2 if _is_fp4(out) else 1)
+    dout = DT_FP4 if cm == 2 else DT_FP8 if out_quant else dtype_code(odt)
     s = _stream(stream, a)
     C.gemm_skinny(
         a=a.data_ptr(), w=w.data_ptr(), c=out.data_ptr(), lda=am * a.stride(0),
-        ldw=am * w.stride(-2), ldc=out.stride(0), M=M, N=N, K=K,
-        din=DT_FP4 if am == 2 else DT_FP8, dout=dtype_code(odt), a_scale=a_scale.data_ptr(),
+        ldw=am * w.stride(-2), ldc=cm * out.stride(0), M=M, N=N, K=K,
+        din=DT_FP4 if am == 2 else DT_FP8, dout=dout, a_scale=a_scale.data_ptr(),
         w_scale=w_scale.data_ptr(), a_scale_ld=a_scale.stride(0), w_scale_ld=w_scale.stride(-2),
         act=ACTS[act], ksplit=S, ws=workspace.data_ptr() if S > 1 else 0,
         offs=offsets.data_ptr() if E else 0, ngroups=E, w_gstride=am * w.stride(0) if E else 0,
-        w_scale_gstride=w_scale.stride(0) if E else 0, stream=s)
+        w_scale_gstride=w_scale.stride(0) if E else 0, stream=s,
+        c_scale=out_scale.data_ptr() if out_quant else 0,
+        c_scale_ld=out_scale.stride(0) if out_quant else 0, glu=int(bool(glu)))
     if stream is not None:  # what was allocated here stays allocated until that stream is done
         out.record_stream(torch.cuda.ExternalStream(s))
         if S > 1:
             workspace.record_stream(torch.cuda.ExternalStream(s))
-    return out
+        if out_quant is not None:
+            out_scale.record_stream(torch.cuda.ExternalStream(s))
+    return out if out_quant is None else (out[:M], out_scale[:M])
 
 
 def gemm_skinny(a, w, out=None, *, a_scale, w_scale, out_dtype=None, act: str = "none",
-                ksplit="auto", workspace=None, stream=None):
+                ksplit="auto", workspace=None, stream=None, glu: bool = False, out_quant=None,
+                out_scale=None):
     """``out = act(a @ w.T)`` for decode shapes, ``M <= 64``, on the weight-streaming split-K
     kernel (``csrc/gemm/gemm_skinny.hip``): block-scaled fp8 (``K % 128 == 0``) or MXFP4
     (``K = 2 * a.shape[1]``, ``K % 256 == 0``) operands with ``a_scale [M, K / 32]`` and
@@ -1181,21 +1211,36 @@ def gemm_skinny(a, w, out=None, *, a_scale, w_scale, out_dtype=None, act: str = 
     every device. Slices write f32 partials into ``workspace`` (float32,
     :func:`skinny_workspace_floats`; allocated here when absent) and a second kernel sums them in
     slice order, applies ``act`` and rounds once: no atomics, two runs write the same bytes.
-    :func:`_check_skinny` holds every refusal."""
+
+    ``glu=True``: ``w`` is the :func:`pack_glu` ``[2F, K]`` weight and the output has ``F = N / 2``
+    columns, ``act(gate) * up`` as :func:`glu_reference` specifies it, one f32 multiply before the
+    one rounding (``N % 64 == 0``). ``out_quant="mx" | "mxfp4"``: the result (after ``act`` or
+    the gated product) leaves as MX data and E8M0 scales, ``(q, s)`` as ``gemm(..., out_quant=)``
+    returns them (``out`` / ``out_scale`` are used when given, larger pitches accepted): the next
+    ``gemm_skinny``'s ``a`` / ``a_scale``. Output columns ``% 128 == 0`` (``"mxfp4"``: 256). Both
+    run in the kernel that writes the output, split or not; the workspace and ``ksplit`` rules
+    keep ``N`` as the rows of ``w``. :func:`_check_skinny` holds every refusal."""
     t = _check_skinny(a, w, None, out, a_scale=a_scale, w_scale=w_scale, out_dtype=out_dtype,
-                      act=act, ksplit=ksplit, workspace=workspace)
-    return _run_skinny(t, a, w, None, out, a_scale, w_scale, act, workspace, stream)
+                      act=act, ksplit=ksplit, workspace=workspace, glu=glu, out_quant=out_quant,
+                      out_scale=out_scale)
+    return _run_skinny(t, a, w, None, out, a_scale, w_scale, act, workspace, stream, glu,
+                       out_quant, out_scale)
 
 
 def gemm_skinny_grouped(a, w, offsets, out=None, *, a_scale, w_scale, out_dtype=None,
-                        act: str = "none", ksplit="auto", workspace=None, stream=None):
+                        act: str = "none", ksplit="auto", workspace=None, stream=None,
+                        glu: bool = False, out_quant=None, out_scale=None):
     """:func:`gemm_skinny` over per-expert weights in one launch, for few rows per expert
     (``<= 64``; more are correct and slow): rows ``[o'[g], o'[g + 1])`` of ``a [T, K]`` times
     ``w[g]`` of ``w [E, N, K]`` under ``w_scale [E, N, K / 32]``. ``offsets`` is the int32
     ``[E + 1]`` device tensor of :func:`gemm_grouped`, read and clamped by the kernels only
     (:func:`clamp_offsets`; no host sync). A group's rows are bit for bit what
     :func:`gemm_skinny` writes for them with the same ``ksplit``; rows outside
-    ``[o'[0], o'[E])`` are not written. The workspace holds ``S * T * N`` floats."""
+    ``[o'[0], o'[E])`` are not written, of ``out_scale`` neither. The workspace holds
+    ``S * T * N`` floats. ``glu`` (``w [E, 2F, K]``, :func:`pack_glu_grouped`) / ``out_quant`` /
+    ``out_scale``: as :func:`gemm_skinny`."""
     t = _check_skinny(a, w, offsets, out, a_scale=a_scale, w_scale=w_scale, out_dtype=out_dtype,
-                      act=act, ksplit=ksplit, workspace=workspace, grouped=True)
-    return _run_skinny(t, a, w, offsets, out, a_scale, w_scale, act, workspace, stream)
+                      act=act, ksplit=ksplit, workspace=workspace, grouped=True, glu=glu,
+                      out_quant=out_quant, out_scale=out_scale)
+    return _run_skinny(t, a, w, offsets, out, a_scale, w_scale, act, workspace, stream, glu,
+                       out_quant, out_scale)

@@ -14,6 +14,12 @@ the shape; grouped: the experts that received rows), the bytes/s that gives, and
 the HBM peak (8.0 TB/s, the MI355X specification).
 
     python scripts/bench_skinny.py --json out/skinny.json
+
+``--fused`` compares, by the same method, two ways of running a gated fc1 on the skinny kernel:
+the chain (f32 ``gemm_skinny``, ``ops.glu.glu``, the row quantiser) and the one fused call
+(``glu=True, out_quant=fmt``): dense M in 1, 16, 64 at N = 2 x 4096, K = 4096 and the two MoE fc1
+shapes. The two write the same bytes, which is checked before anything is timed. ``--shapes moe``
+keeps the MoE shapes only (a kernel-trace run).
 """
 
 from __future__ import annotations
@@ -29,6 +35,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 HBM_PEAK = 8.0e12         # bytes/s, specification
 ROTATE_BYTES = 512 << 20  # weight copies walked through: twice the last-level cache
 DENSE_MS = (1, 4, 16, 64)
+FUSED_MS = (1, 16, 64)
 DENSE_NK = ((4096, 4096), (8192, 8192))
 MOE = dict(E=32, top_k=4, H=4096, F=1536, tokens=(8, 64))
 
@@ -95,7 +102,8 @@ def _measure(variants, nbytes, iters, rounds):
     for k in out:
         out[k]["bytes_per_s"] = nbytes / (out[k]["ms_median"] * 1e-3)
         out[k]["share_of_hbm_peak"] = out[k]["bytes_per_s"] / HBM_PEAK
-    out["skinny_over_tiled"] = out["skinny"]["ms_median"] / out["tiled"]["ms_median"]
+    a, b = list(variants)
+    out[f"{a}_over_{b}"] = out[a]["ms_median"] / out[b]["ms_median"]
     return out
 
 
@@ -151,10 +159,55 @@ def bench_grouped(fmt, tokens, N, K, layer, iters, rounds, gen):
     return r
 
 
+def bench_fused(fmt, rows, N, K, grouped, iters, rounds, gen):
+    """fc1 of a gated layer, ``rows`` rows (grouped: tokens routed top-k over E experts): the
+    chain against the fused call, ``act="silu"``."""
+    import torch
+
+    from ddlb_amd.models.mx_mlp import _fmt_ops
+    from ddlb_amd.ops.gemm import gemm_skinny, gemm_skinny_grouped
+    from ddlb_amd.ops.glu import glu
+
+    E = MOE["E"] if grouped else 1
+    T = rows * MOE["top_k"] if grouped else rows
+    a, sa = _quant((T, K), fmt, gen)
+    w, sw = _quant((E * N, K), fmt, gen, K ** -0.5)
+    pre, used = (), E
+    if grouped:
+        counts = torch.bincount(torch.randint(0, E, (T,), generator=gen, device=gen.device),
+                                minlength=E)
+        offs = torch.zeros(E + 1, dtype=torch.int32, device=gen.device)
+        offs[1:] = torch.cumsum(counts, 0)
+        w, sw, pre, used = w.reshape(E, N, -1), sw.reshape(E, N, -1), (offs,), int((counts > 0).sum())
+    f = gemm_skinny_grouped if grouped else gemm_skinny
+    quant = _fmt_ops(fmt)[0]
+    nbytes = weight_bytes(used * N, K, fmt)
+    sets = _copies(w, sw, weight_bytes(E * N, K, fmt))
+    chain = lambda w, sw: quant(glu(f(a, w, *pre, a_scale=sa, w_scale=sw,          # noqa: E731
+                                      out_dtype=torch.float32), "silu"))
+    fused = lambda w, sw: f(a, w, *pre, a_scale=sa, w_scale=sw, act="silu",        # noqa: E731
+                            glu=True, out_quant=fmt)
+    (q0, s0), (q1, s1) = chain(w, sw), fused(w, sw)
+    torch.cuda.synchronize()
+    assert torch.equal(q0.view(torch.uint8), q1.view(torch.uint8)) and torch.equal(s0, s1)
+    r = _measure({"fused": _cycler(fused, sets), "chain": _cycler(chain, sets)}, nbytes, iters,
+                 rounds)
+    r.update(kind="fused-grouped" if grouped else "fused-dense", layer="fc1", fmt=fmt, M=rows,
+             tokens=rows, T=T, N=N, K=K, weight_bytes=nbytes, copies=len(sets))
+    return r
+
+
 def show(r):
-    what = (f"dense M={r['M']:<3d}" if r["kind"] == "dense"
+    what = (f"dense M={r['M']:<3d}" if r["kind"].endswith("dense")
             else f"moe {r['layer']} tok={r['tokens']:<3d}")
     line = f"{r['fmt']:6s} {what} N={r['N']:<5d} K={r['K']:<5d} {r['weight_bytes'] / 1e6:8.1f} MB"
+    if r["kind"].startswith("fused"):
+        for k in ("fused", "chain"):
+            v = r[k]
+            line += (f" | {k} {v['ms_median'] * 1e3:8.1f} us (min {v['ms_min'] * 1e3:.1f}, "
+                     f"spread {100 * v['spread']:.1f} %)")
+        print(line + f" | fused / chain {r['fused_over_chain']:.3f}", flush=True)
+        return
     for k in ("skinny", "tiled"):
         v = r[k]
         line += (f" | {k} {v['ms_median'] * 1e3:8.1f} us (min {v['ms_min'] * 1e3:.1f}, spread "
@@ -171,6 +224,8 @@ def main(argv=None):
     p.add_argument("--rounds", type=int, default=5)
     p.add_argument("--fmts", default="mx,mxfp4")
     p.add_argument("--json", default="")
+    p.add_argument("--fused", action="store_true", help="gated fc1: the chain against one call")
+    p.add_argument("--shapes", default="all", choices=("all", "moe"), help="with --fused")
     a = p.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("bench_skinny.py measures on a ROCm GPU; none is visible")
@@ -178,7 +233,15 @@ def main(argv=None):
 
     gen = torch.Generator(device="cuda").manual_seed(0)
     rows = []
-    for fmt in a.fmts.split(","):
+    for fmt in a.fmts.split(",") if a.fused else ():
+        for M in FUSED_MS if a.shapes == "all" else ():
+            rows.append(bench_fused(fmt, M, 2 * 4096, 4096, False, a.iters, a.rounds, gen))
+            show(rows[-1])
+        for tokens in MOE["tokens"]:
+            rows.append(bench_fused(fmt, tokens, 2 * MOE["F"], MOE["H"], True, a.iters, a.rounds,
+                                    gen))
+            show(rows[-1])
+    for fmt in () if a.fused else a.fmts.split(","):
         for N, K in DENSE_NK:
             for M in DENSE_MS:
                 rows.append(bench_dense(fmt, M, N, K, a.iters, a.rounds, gen))
