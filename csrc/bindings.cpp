@@ -250,9 +250,9 @@ PYBIND11_MODULE(_C, m) {
            int N, int K, int din, int dout, uintptr_t a_scale, uintptr_t w_scale,
            int64_t a_scale_ld, int64_t w_scale_ld, int act, int ksplit, uintptr_t ws,
            uintptr_t offs, int ngroups, int64_t w_gstride, int64_t w_scale_gstride,
-           uintptr_t stream, uintptr_t c_scale, int64_t c_scale_ld, int glu) {
+           uintptr_t stream, uintptr_t c_scale, int64_t c_scale_ld, int glu, int dw) {
           SkinnyArgs p;
-          p.c_scale = (uint8_t*)c_scale; p.c_scale_ld = c_scale_ld; p.glu = glu;
+          p.c_scale = (uint8_t*)c_scale; p.c_scale_ld = c_scale_ld; p.glu = glu; p.w_dtype = dw;
           p.a = (const void*)a; p.w = (const void*)w; p.c = (void*)c;
           p.a_scale = (const uint8_t*)a_scale; p.w_scale = (const uint8_t*)w_scale;
           p.lda = lda; p.ldw = ldw; p.ldc = ldc;
@@ -269,7 +269,7 @@ PYBIND11_MODULE(_C, m) {
         py::arg("act") = 0, py::arg("ksplit") = 0, py::arg("ws") = 0, py::arg("offs") = 0,
         py::arg("ngroups") = 0, py::arg("w_gstride") = 0, py::arg("w_scale_gstride") = 0,
         py::arg("stream") = 0, py::arg("c_scale") = 0, py::arg("c_scale_ld") = 0,
-        py::arg("glu") = 0);
+        py::arg("glu") = 0, py::arg("dw") = -1);
   // the launch arithmetic of gemm_skinny.h: (strips, the automatic slice count)
   m.def("skinny_plan", [](int N, int nk, int groups, int cus) {
     const int strips = skinny_strips(N);

@@ -140,6 +140,21 @@ struct MmaMX4S {
     acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(b8, a8, acc, 4, 4, 0, sb, 0, sa);
   }
 };
+// The mixed pair (W4A8): the first operand E2M1 (format 4: its first four registers, lane group
+// g's 16 bytes one 32-element block under byte g, as MmaMX4S), the second e4m3 (format 0: all
+// eight registers in the MmaMXS K order, block kb's scale from lane group kb), at the MX-fp8
+// rate. One instruction covers 128 K elements: 64 bytes of the fp4 row, 128 of the fp8 row.
+// Each operand keeps the K map measured for its own format when the two format codes differ
+// (measured: tests/test_gemm_skinny_w4a8_gpu.py, one block at a time under eight different scale
+// bytes per row, is exact for all eight blocks). Skinny kernel only, operand order W (fp4), A
+// (fp8).
+struct MmaMX84S {
+  static __device__ __forceinline__ void step48s(f32x4& acc, const i32x4& b, const i32x8& a,
+                                                 int sb, int sa) {
+    const i32x8 b8 = {b.x, b.y, b.z, b.w, 0, 0, 0, 0};
+    acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(b8, a, acc, 4, 0, 0, sb, 0, sa);
+  }
+};
 template <class Mma, class = void> struct is_fp4 : std::false_type {};
 template <class Mma> struct is_fp4<Mma, std::void_t<decltype(Mma::kFp4)>>
     : std::integral_constant<bool, Mma::kFp4> {};

@@ -18,7 +18,14 @@
 
 namespace ddlb {
 
-// Compile-time choices, picked by measurement (docs/RESULTS.md "Skinny-M GEMM").
+// Compile-time choices, picked by measurement (docs/RESULTS.md "Skinny-M GEMM"). The W4A8 form
+// keeps both numbers with their meanings apart: the ring is kSkinnyPanel W K-tiles (as fp4), the
+// LDS panel kSkinnyPanel 128-byte K-rows of A (as fp8), which is kSkinnyPanel / 2 W K-tiles, so
+// kSkinnyPanel is even for it. A panel as long as the ring would be 64 KiB at 64 rows, over the
+// static LDS limit; a ring as short as the panel (2 tiles) would halve the bytes in flight per
+// wave. This split is the only one timed (docs/RESULTS.md: at the MoE shapes 1.14 - 1.23 x the
+// fp4 form's call time and 0.61 - 0.76 of the fp8 form's); the alternatives were not measured,
+// and are the first thing to try against that gap (the panel barrier falls every two ring steps).
 #ifndef DDLB_SKINNY_NR
 #define DDLB_SKINNY_NR 2
 #endif
@@ -27,6 +34,7 @@ namespace ddlb {
 #endif
 constexpr int kSkinnyNR = DDLB_SKINNY_NR;        // 16-row W tiles per wave (1 or 2)
 constexpr int kSkinnyPanel = DDLB_SKINNY_PANEL;  // K-tiles per A panel in LDS = W K-tiles in flight
+static_assert(kSkinnyPanel % 2 == 0, "the W4A8 panel is whole W K-tiles");
 constexpr int kSkinnyWaves = 4;
 constexpr int kSkinnyStrip = 16 * kSkinnyWaves * kSkinnyNR;  // W rows per workgroup
 constexpr int kSkinnyMaxSlices = 16;             // the cap of the automatic slice count
@@ -36,6 +44,9 @@ static_assert(kSkinnyNR == 1 || kSkinnyNR == 2, "one or two W tiles per wave");
 // byte), scale rows in BYTES, one E8M0 byte per 32 K elements. din DT_FP8 (K % 128 == 0) or DT_FP4
 // (K % 256 == 0); dout bf16 / f16 / f32 (c_scale: DT_FP8 / DT_FP4). Operand rows 16-byte aligned; scale base and row stride
 // multiples of 4 (fp4: 8). Any N >= 1; M == 0 launches nothing.
+// W4A8 (din DT_FP8, w_dtype DT_FP4): a is e4m3, w E2M1 pairs, K % 256 == 0; each operand keeps
+// its own format's rules (lda in bytes = elements and a_scale 4-byte aligned; ldw / w_gstride even
+// and w_scale, with its group stride, 8-byte aligned). fp4 a on fp8 w is refused.
 struct SkinnyArgs {
   const void* a = nullptr;
   const void* w = nullptr;
@@ -71,6 +82,8 @@ struct SkinnyArgs {
   // multiply, then rounded once to dout or quantised (c_scale: [M, N / 64]). ldc >= N / 2. N
   // stays the rows of w: the strips, the slices and the workspace do not change.
   int glu = 0;
+  // w's element type: DT_FP8 or DT_FP4; negative = as din.
+  int w_dtype = -1;
 };
 hipError_t gemm_skinny_launch(const SkinnyArgs& p, int din, int dout, hipStream_t s);
 
@@ -79,7 +92,7 @@ __host__ __device__ inline int skinny_strips(int N) {
   return (int)(((int64_t)N + kSkinnyStrip - 1) / kSkinnyStrip);
 }
 
-// K-tiles (128 bytes of a row: 128 fp8 or 256 fp4 elements) of slice s of S: contiguous, in
+// K-tiles (128 bytes of a row of W: 128 fp8 or 256 fp4 elements) of slice s of S: contiguous, in
 // order, covering [0, nk) exactly once; nk need not divide by S, and S <= nk leaves none empty
 __host__ __device__ inline void skinny_slice(int nk, int S, int s, int& k0, int& k1) {
   k0 = (int)((int64_t)nk * s / S);

@@ -20,6 +20,11 @@ fc1 runs with ``glu=True``, so the product is formed in the GEMM's epilogue and 
 ``act`` only, straight into fc2. ``fused=False`` there is the chain the fused epilogue replaces
 (gated: f32 fc1, ``ops.glu.glu``, the row quantiser; else bf16 fc1 and the row quantiser).
 
+``fmt="w4a8"`` (``kernel="skinny"`` only) keeps the weights in MXFP4 and the activations in
+MX-fp8: ``X`` is quantised with ``quantize_mx``, fc1 writes MX-fp8 (``out_quant="mx"``), and both
+layers run ``gemm_skinny``'s mixed pair, so they stream the fp4 bytes and only the weights pay
+the 4-bit error.
+
 ``reference()`` is the torch chain on the dequantised operands in fp32:
 ``dequantize(quantize_reference(act(Xd @ W1d.T))) @ W2d.T`` (gated: ``glu_reference`` of the
 ``[S, 2F]`` product in place of ``act``).
@@ -27,7 +32,7 @@ fc1 runs with ``glu=True``, so the product is formed in the GEMM's epilogue and 
 
 from __future__ import annotations
 
-FMTS = ("mx", "mxfp4")
+FMTS = ("mx", "mxfp4", "w4a8")
 KERNELS = ("tiled", "skinny")
 SKINNY_ROWS = 64  # the rows one pass over the weights serves (gemm_skinny)
 
@@ -43,6 +48,24 @@ def _fmt_ops(fmt: str):
     raise ValueError(f"fmt must be one of {FMTS}, not {fmt!r}")
 
 
+def _fmt_pair(fmt: str):
+    """``(activation format, weight format)`` of a model format: the same but for ``"w4a8"``."""
+    if fmt not in FMTS:
+        raise ValueError(f"fmt must be one of {FMTS}, not {fmt!r}")
+    return ("mx", "mxfp4") if fmt == "w4a8" else (fmt, fmt)
+
+
+def _check_fmt_kernel(fmt: str, kernel: str) -> int:
+    """The format's refusals that the models share; returns what hidden and ffn are multiples
+    of (the K-tile of the narrower operand)."""
+    afmt, wfmt = _fmt_pair(fmt)
+    if afmt != wfmt and kernel != "skinny":
+        raise ValueError(f"fmt={fmt!r} needs kernel='skinny': only the skinny GEMM multiplies "
+                         "MX-fp8 activations by MXFP4 weights, the tiled kernel takes one "
+                         "format for both operands")
+    return 256 if wfmt == "mxfp4" else 128
+
+
 class MxMLP:
     gated = False  # the ungated block unless the constructor is told otherwise
 
@@ -54,19 +77,19 @@ class MxMLP:
         from ddlb_amd.ops.gemm import ACTS, pack_glu
         from ddlb_amd.primitives.base import torch_dtype, uniform_pm1
 
-        _fmt_ops(fmt)
+        self.afmt, self.wfmt = _fmt_pair(fmt)
         if act not in ACTS:
             raise ValueError(f"act must be one of {tuple(ACTS)}, not {act!r}")
         if dtype not in ("bfloat16", "float16"):
             raise TypeError(f"MxMLP takes bfloat16 / float16 activations, not {dtype}")
-        mod = 256 if fmt == "mxfp4" else 128
+        if kernel not in KERNELS:
+            raise ValueError(f"kernel must be one of {KERNELS}, not {kernel!r}")
+        mod = _check_fmt_kernel(fmt, kernel)
         if hidden % mod or ffn % mod:
             raise ValueError(f"fmt={fmt!r} needs hidden and ffn to be multiples of {mod} "
                              f"(hidden = {hidden}, ffn = {ffn})")
         if seq <= 0:
             raise ValueError("seq must be positive")
-        if kernel not in KERNELS:
-            raise ValueError(f"kernel must be one of {KERNELS}, not {kernel!r}")
         if kernel == "skinny" and seq > SKINNY_ROWS:
             raise ValueError(f"kernel='skinny' is for seq <= {SKINNY_ROWS}, not {seq}: past that "
                              "the tiled kernel is the one to use")
@@ -86,7 +109,7 @@ class MxMLP:
             up = (uniform_pm1((ffn, hidden), "float32", g, dev) * hidden ** -0.5).to(tdt)
             self.W1 = pack_glu(self.W1, up)
         self.W2 = (uniform_pm1((hidden, ffn), "float32", g, dev) * ffn ** -0.5).to(tdt)
-        quant, _, _ = _fmt_ops(fmt)
+        quant, _, _ = _fmt_ops(self.wfmt)
         self.w1q, self.w1s = quant(self.W1)
         self.w2q, self.w2s = quant(self.W2)
         self.out = torch.empty((seq, hidden), dtype=torch.bfloat16, device=dev)
@@ -102,7 +125,7 @@ class MxMLP:
 
         from ddlb_amd.ops.gemm import gemm
 
-        quant, _, _ = _fmt_ops(self.fmt)
+        quant, _, _ = _fmt_ops(self.afmt)
         xq, xs = quant(self.X)
         glu = {"glu": True} if self.gated else {}
         if self.kernel == "skinny":
@@ -122,10 +145,10 @@ class MxMLP:
 
         from ddlb_amd.ops.gemm import gemm_skinny
 
-        quant, _, _ = _fmt_ops(self.fmt)
+        quant, _, _ = _fmt_ops(self.afmt)
         fc1 = dict(a_scale=xs, w_scale=self.w1s)
         if self.fused:
-            hq, hs = gemm_skinny(xq, self.w1q, act=self.act, glu=self.gated, out_quant=self.fmt,
+            hq, hs = gemm_skinny(xq, self.w1q, act=self.act, glu=self.gated, out_quant=self.afmt,
                                  **fc1)
         elif self.gated:
             from ddlb_amd.ops.glu import glu
@@ -141,14 +164,18 @@ class MxMLP:
     def reference_chain(X, W1, W2, act: str = "gelu", fmt: str = "mx", gated: bool = False):
         """The fp32 torch chain on dequantised operands (any device):
         ``dequantize(quantize_reference(act(Xd @ W1d.T))) @ W2d.T``. ``gated``: ``W1`` is the
-        packed ``[2F, H]`` weight and ``glu_reference`` stands in place of ``act``."""
+        packed ``[2F, H]`` weight and ``glu_reference`` stands in place of ``act``. Each operand
+        goes through its own format (``"w4a8"``: ``X`` and ``h`` MX-fp8, the weights MXFP4)."""
         import torch
 
         from ddlb_amd.ops.gemm import ACTS, glu_reference
         from ddlb_amd.parallel.sim import apply_act
 
-        _, qref, deq = _fmt_ops(fmt)
-        xd, w1d, w2d = (deq(*qref(t)) for t in (X, W1, W2))
+        afmt, wfmt = _fmt_pair(fmt)
+        _, qref, deq = _fmt_ops(afmt)
+        _, wqref, wdeq = _fmt_ops(wfmt)
+        xd = deq(*qref(X))
+        w1d, w2d = (wdeq(*wqref(t)) for t in (W1, W2))
         c = (xd @ w1d.t()).to(torch.float32)
         h = glu_reference(c, act) if gated else apply_act(c, ACTS[act]).to(torch.float32)
         return deq(*qref(h)) @ w2d.t()

@@ -38,11 +38,14 @@ goes between it and fc2; ``fused=False`` is the chain the fused epilogue replace
     H  = glu(C)                      ops.glu.glu, f32
     Hq, sH = quantise(H)             the row quantiser
     Yp = Hq W2[e].T                  bf16
+
+``fmt="w4a8"`` (``kernel="skinny"`` only): MXFP4 weights under MX-fp8 activations, as
+:class:`MxMLP` describes it; fc1 writes MX-fp8, so fc2 is the mixed pair too.
 """
 
 from __future__ import annotations
 
-from ddlb_amd.models.mx_mlp import MxMLP, _fmt_ops
+from ddlb_amd.models.mx_mlp import MxMLP, _check_fmt_kernel, _fmt_ops, _fmt_pair
 
 
 def expert_ids(seq: int, experts: int, seed: int = 0):
@@ -99,10 +102,13 @@ class MxMoE:
         from ddlb_amd.ops.gemm import ACTS, MAX_GROUPS, pack_glu_grouped
         from ddlb_amd.primitives.base import uniform_pm1
 
-        quant, _, _ = _fmt_ops(fmt)
+        self.afmt, self.wfmt = _fmt_pair(fmt)
+        quant, _, _ = _fmt_ops(self.wfmt)
         if act not in ACTS:
             raise ValueError(f"act must be one of {tuple(ACTS)}, not {act!r}")
-        mod = 256 if fmt == "mxfp4" else 128
+        if kernel not in KERNELS:
+            raise ValueError(f"kernel must be one of {KERNELS}, not {kernel!r}")
+        mod = _check_fmt_kernel(fmt, kernel)
         if hidden % mod or ffn % mod:
             raise ValueError(f"fmt={fmt!r} needs hidden and ffn to be multiples of {mod} "
                              f"(hidden = {hidden}, ffn = {ffn})")
@@ -112,8 +118,6 @@ class MxMoE:
             raise ValueError("seq must be positive")
         if dispatch not in DISPATCHES:
             raise ValueError(f"dispatch must be one of {DISPATCHES}, not {dispatch!r}")
-        if kernel not in KERNELS:
-            raise ValueError(f"kernel must be one of {KERNELS}, not {kernel!r}")
         if isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 1:
             raise ValueError(f"top_k must be a positive int, not {top_k!r}")
         if top_k > 1 and dispatch != "native":
@@ -176,14 +180,14 @@ class MxMoE:
 
         from ddlb_amd.ops.gemm import gemm_grouped
 
-        quant, _, _ = _fmt_ops(self.fmt)
+        quant, _, _ = _fmt_ops(self.afmt)
         native = self.dispatch == "native"
         if native:
             from ddlb_amd.ops.moe import combine, route
             from ddlb_amd.ops.mx import quantize_mx_gather
 
             offsets, row_token, slot_row = route(self.ids, self.E)
-            xq, xs = quantize_mx_gather(self.X, row_token, fmt=self.fmt)
+            xq, xs = quantize_mx_gather(self.X, row_token, fmt=self.afmt)
         else:
             perm, offsets = self.route()
             xq, xs = quant(self.X.index_select(0, perm))
@@ -191,7 +195,7 @@ class MxMoE:
             from ddlb_amd.ops.gemm import gemm_skinny_grouped
 
             hq, hs = gemm_skinny_grouped(xq, self.w1q, offsets, a_scale=xs, w_scale=self.w1s,
-                                         act=self.act, glu=True, out_quant=self.fmt)
+                                         act=self.act, glu=True, out_quant=self.afmt)
         elif self.kernel == "skinny":
             from ddlb_amd.ops.gemm import gemm_skinny_grouped
             from ddlb_amd.ops.glu import glu

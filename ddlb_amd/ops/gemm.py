@@ -17,7 +17,8 @@ data and E8M0 scales per 32 output columns, quantised in the GEMM's epilogue.
 epilogue writes ``act(gate) * up``, half as many columns, dense or quantised.
 ``gemm_grouped(a, w, offsets)``: per-expert weights ``w [E, N, K]`` over contiguous runs of rows
 of ``a`` given by device-side int32 offsets, one launch, every form above on the tiled kernel.
-``gemm_skinny(a, w)`` / ``gemm_skinny_grouped(a, w, offsets)``: block-scaled fp8 / fp4 operands at
+``gemm_skinny(a, w)`` / ``gemm_skinny_grouped(a, w, offsets)``: block-scaled fp8 / fp4 operands,
+or MX-fp8 ``a`` on MXFP4 ``w`` (W4A8, these two entry points only), at
 decode shapes (``M`` or the rows per expert ``<= 64``) on the weight-streaming split-K kernel
 (``csrc/gemm/gemm_skinny.hip``); nothing above routes to it.
 """
@@ -177,11 +178,16 @@ class _ScaledFormat(NamedTuple):
     plural: bool    # ... and its number
     runs: str       # the subject of the mode message
     tile_note: str
+    w_align: int = 0  # w_scale's alignment where it differs from a_scale's (0: align)
 
 
 _MX_FP8 = _ScaledFormat(1, 128, 4, SCALED_TILES, "block scales", True, "block scales",
                         " (the ping-pong kernels t8 / pt8 / t4 / pt4 take unit scales)")
 _MX_FP4 = _ScaledFormat(2, 256, 8, SCALED_FP4_TILES, "the fp4 GEMM", False, "fp4 operands", "")
+# MX-fp8 a on MXFP4 w (the skinny GEMMs only): a and a_scale by the fp8 rules, w_scale by fp4's
+# (no tiles: no tiled kernel takes the pair, so anything but tile="auto" would be refused)
+_MX_W4A8 = _ScaledFormat(1, 256, 4, (), "the fp8 x fp4 skinny GEMM", False, "fp8 x fp4 operands",
+                         "", w_align=8)
 
 
 def _check_tile(noun, tile, note="", be="is", tiles=SCALED_TILES):
@@ -204,19 +210,20 @@ def _check_block_scaled(f, a, w, a_scale, w_scale, M, tile, mode, a_grp, ksplit)
     K = f.per_byte * a.shape[1]
     if K % f.kmod:
         raise ValueError(f"{f.noun} {need} K % {f.kmod} == 0 (K = {K})")
-    for name, sc, rows in (("a_scale", a_scale, a.shape[0]), ("w_scale", w_scale, w.shape[0])):
+    for name, sc, rows, align in (("a_scale", a_scale, a.shape[0], f.align),
+                                  ("w_scale", w_scale, w.shape[0], f.w_align or f.align)):
         if not isinstance(sc, torch.Tensor) or sc.dtype != torch.uint8:
             raise TypeError(f"{name} must be a uint8 tensor of E8M0 bytes")
         if sc.device != a.device:
             raise ValueError(f"{name} is on {sc.device}, the operands on {a.device}")
         if tuple(sc.shape) != (rows, K // 32):
             raise ValueError(f"{name} must have shape {(rows, K // 32)}, not {tuple(sc.shape)}")
-        if sc.stride(1) != 1 or sc.stride(0) % f.align or sc.stride(0) < K // 32:
+        if sc.stride(1) != 1 or sc.stride(0) % align or sc.stride(0) < K // 32:
             raise ValueError(f"{name} needs unit inner stride and a row stride that is a "
-                             f"multiple of {f.align} (strides {tuple(sc.stride())})")
-        if sc.data_ptr() % f.align:
-            raise ValueError(f"{name} must start at {'an' if f.align == 8 else 'a'} "
-                             f"{f.align}-byte-aligned address")
+                             f"multiple of {align} (strides {tuple(sc.stride())})")
+        if sc.data_ptr() % align:
+            raise ValueError(f"{name} must start at {'an' if align == 8 else 'a'} "
+                             f"{align}-byte-aligned address")
         if rows * sc.stride(0) >= 2 ** 31:
             raise ValueError(f"{name} spans 2 GiB or more")
 
@@ -1058,7 +1065,9 @@ def _check_skinny(a, w, offsets=None, out=None, *, a_scale=None, w_scale=None, o
     (CPU tensors pass through it; the offsets' content is never read). Returns
     ``(M, N, K, E, output dtype, S)``: ``K`` in elements, ``N`` the rows of ``w`` (the output has
     ``N / 2`` columns with ``glu``), ``E = 0`` for the dense form, ``S`` the number of K-slices;
-    with ``out_quant`` the output dtype is the quantised data's."""
+    with ``out_quant`` the output dtype is the quantised data's. The one mixed pair, fp8 ``a`` on
+    fp4 ``w`` of the same ``K`` (``a.shape[1] == 2 * w.shape[-1]``), takes each operand by its own
+    format's rules and ``K % 256 == 0``; ``K-tiles`` (``ksplit``) are ``w``'s, 256 elements."""
     import torch
 
     what = "the grouped skinny GEMM" if grouped else "the skinny GEMM"
@@ -1076,13 +1085,17 @@ def _check_skinny(a, w, offsets=None, out=None, *, a_scale=None, w_scale=None, o
     fp4 = _is_fp4(a) or _is_fp4(w)
     if not fp4 and a.dtype != torch.float8_e4m3fn and w.dtype != torch.float8_e4m3fn:
         raise TypeError(f"{what} takes block-scaled fp8 or fp4 operands, not {a.dtype}")
-    _check_same_dtype(a, w)
+    w4a8 = a.dtype != w.dtype and a.dtype == torch.float8_e4m3fn and _is_fp4(w) \
+        and a.shape[1] == 2 * w.shape[-1]
+    if not w4a8:
+        _check_same_dtype(a, w)
     if a_scale is None or w_scale is None:
         raise ValueError(f"{what} needs a_scale and w_scale (there is no unit-scale kernel)")
     if w.device != a.device:
         raise ValueError("operands on different devices")
-    _check_k(a, w)
-    f = _MX_FP4 if fp4 else _MX_FP8
+    if not w4a8:
+        _check_k(a, w)
+    f = _MX_W4A8 if w4a8 else _MX_FP4 if fp4 else _MX_FP8
     M, N, K = a.shape[0], w.shape[-2], f.per_byte * a.shape[1]
     E = w.shape[0] if grouped else 0
     if N < 1:
@@ -1105,8 +1118,9 @@ def _check_skinny(a, w, offsets=None, out=None, *, a_scale=None, w_scale=None, o
         if not isinstance(w_scale, torch.Tensor) or w_scale.dim() != 3:
             raise ValueError(f"w_scale must have shape {(E, N, K // 32)}, not "
                              f"{tuple(getattr(w_scale, 'shape', ()))}")
-        if w_scale.stride(0) % f.align or (E > 1 and w_scale.stride(0) < N * w_scale.stride(1)):
-            raise ValueError(f"w_scale needs experts a multiple of {f.align} bytes and at least "
+        wal = f.w_align or f.align
+        if w_scale.stride(0) % wal or (E > 1 and w_scale.stride(0) < N * w_scale.stride(1)):
+            raise ValueError(f"w_scale needs experts a multiple of {wal} bytes and at least "
                              f"N rows apart (strides {tuple(w_scale.stride())})")
     for name, t in (("a", a), ("w", w)):
         if t.stride(-1) != 1 or t.stride(-2) < t.shape[-1]:
@@ -1174,18 +1188,20 @@ def _run_skinny(t, a, w, offsets, out, a_scale, w_scale, act, workspace, stream,
         workspace = torch.empty(skinny_workspace_floats(S, M, N), dtype=torch.float32,
                                 device=a.device)
     am, cm = (2 if _is_fp4(a) else 1), (2 if _is_fp4(out) else 1)
+    wm = am if w.dtype == a.dtype else 2 if _is_fp4(w) else 1  # (W4A8: w by its own dtype)
     dout = DT_FP4 if cm == 2 else DT_FP8 if out_quant else dtype_code(odt)
     s = _stream(stream, a)
     C.gemm_skinny(
         a=a.data_ptr(), w=w.data_ptr(), c=out.data_ptr(), lda=am * a.stride(0),
-        ldw=am * w.stride(-2), ldc=cm * out.stride(0), M=M, N=N, K=K,
+        ldw=wm * w.stride(-2), ldc=cm * out.stride(0), M=M, N=N, K=K,
         din=DT_FP4 if am == 2 else DT_FP8, dout=dout, a_scale=a_scale.data_ptr(),
         w_scale=w_scale.data_ptr(), a_scale_ld=a_scale.stride(0), w_scale_ld=w_scale.stride(-2),
         act=ACTS[act], ksplit=S, ws=workspace.data_ptr() if S > 1 else 0,
-        offs=offsets.data_ptr() if E else 0, ngroups=E, w_gstride=am * w.stride(0) if E else 0,
+        offs=offsets.data_ptr() if E else 0, ngroups=E, w_gstride=wm * w.stride(0) if E else 0,
         w_scale_gstride=w_scale.stride(0) if E else 0, stream=s,
         c_scale=out_scale.data_ptr() if out_quant else 0,
-        c_scale_ld=out_scale.stride(0) if out_quant else 0, glu=int(bool(glu)))
+        c_scale_ld=out_scale.stride(0) if out_quant else 0, glu=int(bool(glu)),
+        dw=DT_FP4 if wm == 2 else DT_FP8)
     if stream is not None:  # what was allocated here stays allocated until that stream is done
         out.record_stream(torch.cuda.ExternalStream(s))
         if S > 1:
@@ -1202,12 +1218,16 @@ def gemm_skinny(a, w, out=None, *, a_scale, w_scale, out_dtype=None, act: str = 
     kernel (``csrc/gemm/gemm_skinny.hip``): block-scaled fp8 (``K % 128 == 0``) or MXFP4
     (``K = 2 * a.shape[1]``, ``K % 256 == 0``) operands with ``a_scale [M, K / 32]`` and
     ``w_scale [N, K / 32]`` as :func:`gemm` takes them, any ``N >= 1``, output bf16 (default) /
-    f16 / f32. The weights are read once for up to 64 rows and never staged through LDS; any
-    ``M`` is correct, but past 64 rows they are streamed once per 64 rows and :func:`gemm` is the
-    kernel to use.
+    f16 / f32. W4A8: ``a`` float8_e4m3fn ``[M, K]`` on ``w`` float4_e2m1fn_x2 ``[N, K / 2]``
+    (accepted exactly when ``a.shape[1] == 2 * w.shape[-1]``), ``K % 256 == 0``, ``a_scale`` by
+    the fp8 rules (4-byte aligned), ``w_scale`` by the fp4 rules (8-byte aligned): the fp4 form's
+    weight bytes with 8-bit activations. Any other dtype mismatch is a ``TypeError``. The weights
+    are read once for up to 64 rows and never staged through LDS; any ``M`` is correct, but past
+    64 rows they are streamed once per 64 rows and :func:`gemm` is the kernel to use.
 
     ``ksplit``: the number of K-slices, ``"auto"`` (:func:`skinny_auto_slices`, which depends on
-    the device's CU count) or an int in ``1 .. nk`` K-tiles, which fixes the summation order on
+    the device's CU count) or an int in ``1 .. nk`` K-tiles (128 bytes of a row of ``w``: W4A8
+    counts 256 elements, as fp4), which fixes the summation order on
     every device. Slices write f32 partials into ``workspace`` (float32,
     :func:`skinny_workspace_floats`; allocated here when absent) and a second kernel sums them in
     slice order, applies ``act`` and rounds once: no atomics, two runs write the same bytes.
@@ -1237,7 +1257,8 @@ def gemm_skinny_grouped(a, w, offsets, out=None, *, a_scale, w_scale, out_dtype=
     (:func:`clamp_offsets`; no host sync). A group's rows are bit for bit what
     :func:`gemm_skinny` writes for them with the same ``ksplit``; rows outside
     ``[o'[0], o'[E])`` are not written, of ``out_scale`` neither. The workspace holds
-    ``S * T * N`` floats. ``glu`` (``w [E, 2F, K]``, :func:`pack_glu_grouped`) / ``out_quant`` /
+    ``S * T * N`` floats. W4A8: ``w [E, N, K / 2]`` float4_e2m1fn_x2 under fp8 ``a``, as
+    :func:`gemm_skinny`. ``glu`` (``w [E, 2F, K]``, :func:`pack_glu_grouped`) / ``out_quant`` /
     ``out_scale``: as :func:`gemm_skinny`."""
     t = _check_skinny(a, w, offsets, out, a_scale=a_scale, w_scale=w_scale, out_dtype=out_dtype,
                       act=act, ksplit=ksplit, workspace=workspace, grouped=True, glu=glu,

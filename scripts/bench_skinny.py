@@ -3,11 +3,14 @@
 In ONE process, alternating per shape: ``gemm_skinny`` against ``gemm`` (dense: M in 1, 4, 16, 64
 times (N, K) in (4096, 4096), (8192, 8192)) and ``gemm_skinny_grouped`` against ``gemm_grouped``
 (E = 32 experts, 8 and 64 tokens routed top-4, H = 4096, F = 1536: the fc1 and fc2 shapes), MX-fp8
-and MXFP4. Before anything is timed the two outputs are compared on the same seeded inputs
-(``atol = 1e-3 K``: both accumulate in f32, in different orders). Every shape is warmed; device
-events surround ``iters`` back-to-back calls; variants alternate over ``rounds`` rounds and the
-median, minimum and round-to-round spread are reported. Successive calls walk through copies of
-the weights that together exceed the 256 MB last-level cache, so the weights come from HBM.
+and MXFP4. ``w4a8`` (MX-fp8 activations on MXFP4 weights) is a third format column over the same
+shapes: only the skinny kernel takes it, so its rows have no tiled time and its output is checked
+against the product of the dequantised operands. Before anything is timed the two outputs are
+compared on the same seeded inputs (``atol = 1e-3 K``: both accumulate in f32, in different
+orders). Every shape is warmed; device events surround ``iters`` back-to-back calls; variants
+alternate over ``rounds`` rounds and the median, minimum and round-to-round spread are reported.
+Successive calls walk through copies of the weights that together exceed the 256 MB last-level
+cache, so the weights come from HBM.
 
 Printed per row: time per call, the weight-plus-scale bytes the shape needs (computed here from
 the shape; grouped: the experts that received rows), the bytes/s that gives, and its share of
@@ -63,16 +66,27 @@ def summarise(ts):
 
 def weight_bytes(rows, K, fmt):
     """Data plus scale bytes of ``rows`` weight rows of K elements."""
-    return rows * (K // (2 if fmt == "mxfp4" else 1) + K // 32)
+    return rows * (K // (1 if fmt == "mx" else 2) + K // 32)
 
 
-def _quant(shape, fmt, gen, scale=1.0):
+def _quant(shape, fmt, gen, scale=1.0, weight=False):
+    """Random bf16 data quantised as the activations of ``fmt``, or as its weights."""
     import torch
 
-    from ddlb_amd.models.mx_mlp import _fmt_ops
+    from ddlb_amd.models.mx_mlp import _fmt_ops, _fmt_pair
 
     x = torch.randn(shape, generator=gen, device=gen.device, dtype=torch.bfloat16) * scale
-    return _fmt_ops(fmt)[0](x)
+    return _fmt_ops(_fmt_pair(fmt)[weight])[0](x)
+
+
+def _check_mixed(out, a, sa, w, sw, K):
+    """``w4a8`` has no tiled kernel to compare with: the dequantised operands' product."""
+    import torch
+
+    from ddlb_amd.ops import mx
+
+    ref = mx.dequantize_mx(a, sa) @ mx.dequantize_mxfp4(w, sw).t()
+    torch.testing.assert_close(out.float(), ref, rtol=2.0 ** -7, atol=1e-3 * K)
 
 
 def _copies(q, s, nbytes):
@@ -102,8 +116,9 @@ def _measure(variants, nbytes, iters, rounds):
     for k in out:
         out[k]["bytes_per_s"] = nbytes / (out[k]["ms_median"] * 1e-3)
         out[k]["share_of_hbm_peak"] = out[k]["bytes_per_s"] / HBM_PEAK
-    a, b = list(variants)
-    out[f"{a}_over_{b}"] = out[a]["ms_median"] / out[b]["ms_median"]
+    if len(variants) == 2:
+        a, b = list(variants)
+        out[f"{a}_over_{b}"] = out[a]["ms_median"] / out[b]["ms_median"]
     return out
 
 
@@ -113,18 +128,23 @@ def bench_dense(fmt, M, N, K, iters, rounds, gen):
     from ddlb_amd.ops.gemm import gemm, gemm_skinny
 
     a, sa = _quant((M, K), fmt, gen)
-    w, sw = _quant((N, K), fmt, gen, K ** -0.5)
+    w, sw = _quant((N, K), fmt, gen, K ** -0.5, weight=True)
     nbytes = weight_bytes(N, K, fmt)
     sets = _copies(w, sw, nbytes)
     out_s = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
     out_t = torch.empty_like(out_s)
     skinny = lambda w, sw: gemm_skinny(a, w, out_s, a_scale=sa, w_scale=sw)       # noqa: E731
     tiled = lambda w, sw: gemm(a, w, out_t, a_scale=sa, w_scale=sw)               # noqa: E731
-    skinny(w, sw), tiled(w, sw)
-    torch.cuda.synchronize()
-    torch.testing.assert_close(out_s.float(), out_t.float(), rtol=2.0 ** -7, atol=1e-3 * K)
-    r = _measure({"skinny": _cycler(skinny, sets), "tiled": _cycler(tiled, sets)}, nbytes, iters,
-                 rounds)
+    variants = {"skinny": _cycler(skinny, sets)}
+    skinny(w, sw)
+    if fmt == "w4a8":
+        _check_mixed(out_s, a, sa, w, sw, K)
+    else:
+        tiled(w, sw)
+        torch.cuda.synchronize()
+        torch.testing.assert_close(out_s.float(), out_t.float(), rtol=2.0 ** -7, atol=1e-3 * K)
+        variants["tiled"] = _cycler(tiled, sets)
+    r = _measure(variants, nbytes, iters, rounds)
     r.update(kind="dense", fmt=fmt, M=M, N=N, K=K, weight_bytes=nbytes, copies=len(sets))
     return r
 
@@ -140,7 +160,7 @@ def bench_grouped(fmt, tokens, N, K, layer, iters, rounds, gen):
     offs = torch.zeros(E + 1, dtype=torch.int32, device=gen.device)
     offs[1:] = torch.cumsum(counts, 0)
     a, sa = _quant((T, K), fmt, gen)
-    w, sw = _quant((E * N, K), fmt, gen, K ** -0.5)
+    w, sw = _quant((E * N, K), fmt, gen, K ** -0.5, weight=True)
     w, sw = w.reshape(E, N, -1), sw.reshape(E, N, -1)
     nbytes = weight_bytes(int((counts > 0).sum()) * N, K, fmt)
     sets = _copies(w, sw, weight_bytes(E * N, K, fmt))
@@ -149,11 +169,18 @@ def bench_grouped(fmt, tokens, N, K, layer, iters, rounds, gen):
     skinny = lambda w, sw: gemm_skinny_grouped(a, w, offs, out_s, a_scale=sa,      # noqa: E731
                                                w_scale=sw)
     tiled = lambda w, sw: gemm_grouped(a, w, offs, out_t, a_scale=sa, w_scale=sw)  # noqa: E731
-    skinny(w, sw), tiled(w, sw)
-    torch.cuda.synchronize()
-    torch.testing.assert_close(out_s.float(), out_t.float(), rtol=2.0 ** -7, atol=1e-3 * K)
-    r = _measure({"skinny": _cycler(skinny, sets), "tiled": _cycler(tiled, sets)}, nbytes, iters,
-                 rounds)
+    variants = {"skinny": _cycler(skinny, sets)}
+    skinny(w, sw)
+    if fmt == "w4a8":  # the expert with the most rows, against the dequantised operands
+        e = int(counts.argmax())
+        rows = slice(int(offs[e]), int(offs[e + 1]))
+        _check_mixed(out_s[rows], a[rows], sa[rows], w[e], sw[e], K)
+    else:
+        tiled(w, sw)
+        torch.cuda.synchronize()
+        torch.testing.assert_close(out_s.float(), out_t.float(), rtol=2.0 ** -7, atol=1e-3 * K)
+        variants["tiled"] = _cycler(tiled, sets)
+    r = _measure(variants, nbytes, iters, rounds)
     r.update(kind="grouped", layer=layer, fmt=fmt, tokens=tokens, T=T, E=E, N=N, K=K,
              experts_with_rows=int((counts > 0).sum()), weight_bytes=nbytes, copies=len(sets))
     return r
@@ -164,14 +191,15 @@ def bench_fused(fmt, rows, N, K, grouped, iters, rounds, gen):
     chain against the fused call, ``act="silu"``."""
     import torch
 
-    from ddlb_amd.models.mx_mlp import _fmt_ops
+    from ddlb_amd.models.mx_mlp import _fmt_ops, _fmt_pair
     from ddlb_amd.ops.gemm import gemm_skinny, gemm_skinny_grouped
     from ddlb_amd.ops.glu import glu
 
     E = MOE["E"] if grouped else 1
     T = rows * MOE["top_k"] if grouped else rows
+    afmt = _fmt_pair(fmt)[0]  # what fc1 writes: the activations' format
     a, sa = _quant((T, K), fmt, gen)
-    w, sw = _quant((E * N, K), fmt, gen, K ** -0.5)
+    w, sw = _quant((E * N, K), fmt, gen, K ** -0.5, weight=True)
     pre, used = (), E
     if grouped:
         counts = torch.bincount(torch.randint(0, E, (T,), generator=gen, device=gen.device),
@@ -180,13 +208,13 @@ def bench_fused(fmt, rows, N, K, grouped, iters, rounds, gen):
         offs[1:] = torch.cumsum(counts, 0)
         w, sw, pre, used = w.reshape(E, N, -1), sw.reshape(E, N, -1), (offs,), int((counts > 0).sum())
     f = gemm_skinny_grouped if grouped else gemm_skinny
-    quant = _fmt_ops(fmt)[0]
+    quant = _fmt_ops(afmt)[0]
     nbytes = weight_bytes(used * N, K, fmt)
     sets = _copies(w, sw, weight_bytes(E * N, K, fmt))
     chain = lambda w, sw: quant(glu(f(a, w, *pre, a_scale=sa, w_scale=sw,          # noqa: E731
                                       out_dtype=torch.float32), "silu"))
     fused = lambda w, sw: f(a, w, *pre, a_scale=sa, w_scale=sw, act="silu",        # noqa: E731
-                            glu=True, out_quant=fmt)
+                            glu=True, out_quant=afmt)
     (q0, s0), (q1, s1) = chain(w, sw), fused(w, sw)
     torch.cuda.synchronize()
     assert torch.equal(q0.view(torch.uint8), q1.view(torch.uint8)) and torch.equal(s0, s1)
@@ -209,11 +237,15 @@ def show(r):
         print(line + f" | fused / chain {r['fused_over_chain']:.3f}", flush=True)
         return
     for k in ("skinny", "tiled"):
+        if k not in r:
+            continue
         v = r[k]
         line += (f" | {k} {v['ms_median'] * 1e3:8.1f} us (min {v['ms_min'] * 1e3:.1f}, spread "
                  f"{100 * v['spread']:.1f} %) {v['bytes_per_s'] / 1e12:5.2f} TB/s "
                  f"{100 * v['share_of_hbm_peak']:5.1f} % of peak")
-    print(line + f" | skinny / tiled {r['skinny_over_tiled']:.3f}", flush=True)
+    if "tiled" in r:
+        line += f" | skinny / tiled {r['skinny_over_tiled']:.3f}"
+    print(line, flush=True)
 
 
 def main(argv=None):
@@ -222,7 +254,7 @@ def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     p.add_argument("--iters", type=int, default=300)
     p.add_argument("--rounds", type=int, default=5)
-    p.add_argument("--fmts", default="mx,mxfp4")
+    p.add_argument("--fmts", default="mx,mxfp4,w4a8")
     p.add_argument("--json", default="")
     p.add_argument("--fused", action="store_true", help="gated fc1: the chain against one call")
     p.add_argument("--shapes", default="all", choices=("all", "moe"), help="with --fused")
