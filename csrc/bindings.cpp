@@ -270,6 +270,30 @@ PYBIND11_MODULE(_C, m) {
         py::arg("ngroups") = 0, py::arg("w_gstride") = 0, py::arg("w_scale_gstride") = 0,
         py::arg("stream") = 0, py::arg("c_scale") = 0, py::arg("c_scale_ld") = 0,
         py::arg("glu") = 0, py::arg("dw") = -1);
+  // The A16 skinny GEMM (gemm_skinny_a16_launch): a bf16 / f16 (din), w MXFP4 / MX-fp8 under
+  // w_scale (dw = DT_FP4 / DT_FP8) or of a's dtype (dw < 0, w_scale 0); no quantised output.
+  m.def("gemm_skinny_a16",
+        [](uintptr_t a, uintptr_t w, uintptr_t c, int64_t lda, int64_t ldw, int64_t ldc, int M,
+           int N, int K, int din, int dout, int dw, uintptr_t w_scale, int64_t w_scale_ld, int act,
+           int ksplit, uintptr_t ws, uintptr_t offs, int ngroups, int64_t w_gstride,
+           int64_t w_scale_gstride, uintptr_t stream, int glu) {
+          SkinnyArgs p;
+          p.a = (const void*)a; p.w = (const void*)w; p.c = (void*)c;
+          p.w_scale = (const uint8_t*)w_scale; p.w_scale_ld = w_scale_ld;
+          p.lda = lda; p.ldw = ldw; p.ldc = ldc;
+          p.M = M; p.N = N; p.K = K;
+          p.act = act; p.ksplit = ksplit; p.ws = (float*)ws;
+          p.offs = (const int*)offs; p.ngroups = ngroups;
+          p.w_gstride = w_gstride; p.w_scale_gstride = w_scale_gstride;
+          p.glu = glu; p.w_dtype = dw;
+          check(gemm_skinny_a16_launch(p, din, dout, (hipStream_t)stream), "gemm_skinny_a16");
+        },
+        py::arg("a"), py::arg("w"), py::arg("c"), py::arg("lda"), py::arg("ldw"), py::arg("ldc"),
+        py::arg("M"), py::arg("N"), py::arg("K"), py::arg("din"), py::arg("dout"),
+        py::arg("dw") = -1, py::arg("w_scale") = 0, py::arg("w_scale_ld") = 0, py::arg("act") = 0,
+        py::arg("ksplit") = 0, py::arg("ws") = 0, py::arg("offs") = 0, py::arg("ngroups") = 0,
+        py::arg("w_gstride") = 0, py::arg("w_scale_gstride") = 0, py::arg("stream") = 0,
+        py::arg("glu") = 0);
   // the launch arithmetic of gemm_skinny.h: (strips, the automatic slice count)
   m.def("skinny_plan", [](int N, int nk, int groups, int cus) {
     const int strips = skinny_strips(N);

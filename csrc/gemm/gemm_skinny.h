@@ -87,6 +87,16 @@ struct SkinnyArgs {
 };
 hipError_t gemm_skinny_launch(const SkinnyArgs& p, int din, int dout, hipStream_t s);
 
+// The A16 family (csrc/gemm/gemm_skinny_a16.hip): a is bf16 or f16 (din DT_BF16 / DT_F16), never
+// quantised, a_scale null. w_dtype says what w is: DT_FP4 (MXFP4: E2M1 pairs, K % 256 == 0) or
+// DT_FP8 (MX-fp8, K % 128 == 0), both under w_scale, expanded to din in registers as
+// e * 2^(s - 127); or negative, w of din's own dtype (K % 64 == 0) and w_scale null. A K-tile
+// (ksplit) stays 128 bytes of a row of W: 256 / 128 / 64 elements. lda, ldw, w_gstride in ELEMENTS
+// as above, rows 16-byte aligned, w_scale 4-byte aligned (fp4: 8). dout is din or DT_F32; no
+// quantised output (c_scale null). Strips, slices, the workspace, the grouped form, act and glu are
+// as above.
+hipError_t gemm_skinny_a16_launch(const SkinnyArgs& p, int din, int dout, hipStream_t s);
+
 // strips of N weight rows (the last one may be ragged)
 __host__ __device__ inline int skinny_strips(int N) {
   return (int)(((int64_t)N + kSkinnyStrip - 1) / kSkinnyStrip);

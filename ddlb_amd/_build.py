@@ -53,6 +53,7 @@ SOURCES = [  # heaviest translation units first (the parallel build's critical p
     "gemm/gemm_mxs.hip",
     "gemm/gemm_mx4.hip",
     "gemm/gemm_skinny.hip",
+    "gemm/gemm_skinny_a16.hip",
     "gemm/mx_quant.hip",
     "gemm/mx_quant_t.hip",
     "gemm/gemm_generic.hip",
@@ -70,14 +71,15 @@ SOURCES = [  # heaviest translation units first (the parallel build's critical p
     "bindings.cpp",
 ]
 # Per-source compiler flags. The skinny GEMM is built without the packed-f32 VALU instructions
-# (v_pk_add / mul / fma_f32): its epilogue and reduce arithmetic stays scalar f32.
-EXTRA_FLAGS = {"gemm/gemm_skinny.hip": ["-Xclang", "-target-feature", "-Xclang",
-                                        "-packed-fp32-ops"]}
+# (v_pk_add / mul / fma_f32): its epilogue and reduce arithmetic stays scalar f32. The A16 form
+# shares that code as source (gemm_skinny_tail.h) and is built the same way.
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA_FLAGS = {"gemm/gemm_skinny.hip": _NO_PK_F32, "gemm/gemm_skinny_a16.hip": _NO_PK_F32}
 HEADERS = ["gemm/gemm.h", "gemm/gemm_kernels.h", "gemm/gemm_entry.h", "gemm/tile_map.h",
            "gemm/device_info.h", "gemm/mx_cvt.h", "gemm/mx_quant_in.h", "gemm/row_io.h",
            "gemm/glu_act.h", "gemm/gemm_grouped_kernels.h", "gemm/gemm_kgrouped_kernels.h",
-           "gemm/gemm_skinny.h", "moe/moe.h", "moe/moe_route_map.h", "runtime/kernels.h", "comm/comm.h",
-           "runtime/plan.h", "runtime/plan_ir.h"]
+           "gemm/gemm_skinny.h", "gemm/gemm_skinny_tail.h", "moe/moe.h", "moe/moe_route_map.h",
+           "runtime/kernels.h", "comm/comm.h", "runtime/plan.h", "runtime/plan_ir.h"]
 
 
 def ext_path() -> str:

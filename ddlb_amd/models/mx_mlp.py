@@ -25,6 +25,12 @@ MX-fp8: ``X`` is quantised with ``quantize_mx``, fc1 writes MX-fp8 (``out_quant=
 layers run ``gemm_skinny``'s mixed pair, so they stream the fp4 bytes and only the weights pay
 the 4-bit error.
 
+``fmt="w4a16"`` / ``"w8a16"`` (``kernel="skinny"`` only) is weight-only quantisation: MXFP4 /
+MX-fp8 weights, ``X`` and ``H`` stay 16-bit and nothing is quantised per forward. Both layers run
+``ops.gemm.gemm_skinny_a16`` (fc1 with ``act`` / ``glu``, writing ``H`` in ``X``'s dtype).
+``reference_chain`` for them: the dequantised weights, ``H`` rounded to ``X``'s dtype between the
+layers.
+
 ``reference()`` is the torch chain on the dequantised operands in fp32:
 ``dequantize(quantize_reference(act(Xd @ W1d.T))) @ W2d.T`` (gated: ``glu_reference`` of the
 ``[S, 2F]`` product in place of ``act``).
@@ -32,7 +38,8 @@ the 4-bit error.
 
 from __future__ import annotations
 
-FMTS = ("mx", "mxfp4", "w4a8")
+FMTS = ("mx", "mxfp4", "w4a8", "w4a16", "w8a16")
+A16 = "a16"  # the activation "format" of the weight-only formats: not quantised
 KERNELS = ("tiled", "skinny")
 SKINNY_ROWS = 64  # the rows one pass over the weights serves (gemm_skinny)
 
@@ -49,10 +56,12 @@ def _fmt_ops(fmt: str):
 
 
 def _fmt_pair(fmt: str):
-    """``(activation format, weight format)`` of a model format: the same but for ``"w4a8"``."""
+    """``(activation format, weight format)`` of a model format: the same but for ``"w4a8"`` and
+    the weight-only formats (activations :data:`A16`)."""
     if fmt not in FMTS:
         raise ValueError(f"fmt must be one of {FMTS}, not {fmt!r}")
-    return ("mx", "mxfp4") if fmt == "w4a8" else (fmt, fmt)
+    mixed = {"w4a8": ("mx", "mxfp4"), "w4a16": (A16, "mxfp4"), "w8a16": (A16, "mx")}
+    return mixed.get(fmt, (fmt, fmt))
 
 
 def _check_fmt_kernel(fmt: str, kernel: str) -> int:
@@ -60,9 +69,9 @@ def _check_fmt_kernel(fmt: str, kernel: str) -> int:
     of (the K-tile of the narrower operand)."""
     afmt, wfmt = _fmt_pair(fmt)
     if afmt != wfmt and kernel != "skinny":
-        raise ValueError(f"fmt={fmt!r} needs kernel='skinny': only the skinny GEMM multiplies "
-                         "MX-fp8 activations by MXFP4 weights, the tiled kernel takes one "
-                         "format for both operands")
+        raise ValueError(f"fmt={fmt!r} needs kernel='skinny': only the skinny GEMMs multiply "
+                         "MX-fp8 or 16-bit activations by narrower MX weights, the tiled kernel "
+                         "takes one format for both operands")
     return 256 if wfmt == "mxfp4" else 128
 
 
@@ -112,7 +121,8 @@ class MxMLP:
         quant, _, _ = _fmt_ops(self.wfmt)
         self.w1q, self.w1s = quant(self.W1)
         self.w2q, self.w2s = quant(self.W2)
-        self.out = torch.empty((seq, hidden), dtype=torch.bfloat16, device=dev)
+        odt = tdt if self.afmt == A16 else torch.bfloat16  # weight-only: X's dtype throughout
+        self.out = torch.empty((seq, hidden), dtype=odt, device=dev)
         torch.cuda.synchronize()
 
     @property
@@ -125,6 +135,11 @@ class MxMLP:
 
         from ddlb_amd.ops.gemm import gemm
 
+        if self.afmt == A16:  # weight-only: nothing is quantised per forward
+            from ddlb_amd.ops.gemm import gemm_skinny_a16
+
+            h = gemm_skinny_a16(self.X, self.w1q, w_scale=self.w1s, act=self.act, glu=self.gated)
+            return gemm_skinny_a16(h, self.w2q, self.out, w_scale=self.w2s)
         quant, _, _ = _fmt_ops(self.afmt)
         xq, xs = quant(self.X)
         glu = {"glu": True} if self.gated else {}
@@ -172,13 +187,20 @@ class MxMLP:
         from ddlb_amd.parallel.sim import apply_act
 
         afmt, wfmt = _fmt_pair(fmt)
-        _, qref, deq = _fmt_ops(afmt)
         _, wqref, wdeq = _fmt_ops(wfmt)
-        xd = deq(*qref(X))
+        if afmt == A16:  # not quantised: X as it is, h rounded to X's dtype between the layers
+            def through(t):
+                return t.to(X.dtype).to(torch.float32)
+        else:
+            _, qref, deq = _fmt_ops(afmt)
+
+            def through(t):
+                return deq(*qref(t))
+        xd = through(X)
         w1d, w2d = (wdeq(*wqref(t)) for t in (W1, W2))
         c = (xd @ w1d.t()).to(torch.float32)
         h = glu_reference(c, act) if gated else apply_act(c, ACTS[act]).to(torch.float32)
-        return deq(*qref(h)) @ w2d.t()
+        return through(h) @ w2d.t()
 
     def reference(self):
         return self.reference_chain(self.X, self.W1, self.W2, self.act, self.fmt, self.gated)

@@ -41,11 +41,15 @@ goes between it and fc2; ``fused=False`` is the chain the fused epilogue replace
 
 ``fmt="w4a8"`` (``kernel="skinny"`` only): MXFP4 weights under MX-fp8 activations, as
 :class:`MxMLP` describes it; fc1 writes MX-fp8, so fc2 is the mixed pair too.
+
+``fmt="w4a16"`` / ``"w8a16"`` (``kernel="skinny"`` only): weight-only quantisation. The routed
+rows stay bf16 (``ops.moe.gather``, or ``index_select`` with the torch dispatch) and both layers
+run ``ops.gemm.gemm_skinny_a16_grouped``, fc1 gated and writing bf16.
 """
 
 from __future__ import annotations
 
-from ddlb_amd.models.mx_mlp import MxMLP, _check_fmt_kernel, _fmt_ops, _fmt_pair
+from ddlb_amd.models.mx_mlp import A16, MxMLP, _check_fmt_kernel, _fmt_ops, _fmt_pair
 
 
 def expert_ids(seq: int, experts: int, seed: int = 0):
@@ -180,6 +184,8 @@ class MxMoE:
 
         from ddlb_amd.ops.gemm import gemm_grouped
 
+        if self.afmt == A16:
+            return self._forward_a16()
         quant, _, _ = _fmt_ops(self.afmt)
         native = self.dispatch == "native"
         if native:
@@ -217,6 +223,27 @@ class MxMoE:
             gemm_grouped(hq, self.w2q, offsets, self.ysorted, a_scale=hs, w_scale=self.w2s,
                          tile=self.tile)
         if native:
+            combine(self.ysorted, slot_row, self.gates, out=self.out)
+        else:
+            self.out.index_copy_(0, perm, self.ysorted)
+        return self.out
+
+    def _forward_a16(self):
+        """The weight-only formats: the routed rows stay bf16, nothing is quantised."""
+        from ddlb_amd.ops.gemm import gemm_skinny_a16_grouped
+
+        if self.dispatch == "native":
+            from ddlb_amd.ops.moe import combine, gather, route
+
+            offsets, row_token, slot_row = route(self.ids, self.E)
+            xp = gather(self.X, row_token)
+        else:
+            perm, offsets = self.route()
+            xp = self.X.index_select(0, perm)
+        h = gemm_skinny_a16_grouped(xp, self.w1q, offsets, w_scale=self.w1s, act=self.act,
+                                    glu=True)
+        gemm_skinny_a16_grouped(h, self.w2q, offsets, self.ysorted, w_scale=self.w2s)
+        if self.dispatch == "native":
             combine(self.ysorted, slot_row, self.gates, out=self.out)
         else:
             self.out.index_copy_(0, perm, self.ysorted)

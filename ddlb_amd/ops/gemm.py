@@ -21,6 +21,9 @@ of ``a`` given by device-side int32 offsets, one launch, every form above on the
 or MX-fp8 ``a`` on MXFP4 ``w`` (W4A8, these two entry points only), at
 decode shapes (``M`` or the rows per expert ``<= 64``) on the weight-streaming split-K kernel
 (``csrc/gemm/gemm_skinny.hip``); nothing above routes to it.
+``gemm_skinny_a16(a, w)`` / ``gemm_skinny_a16_grouped(a, w, offsets)``: the same shapes for bf16 /
+f16 ``a`` that is not quantised, on MXFP4 (W4A16), MX-fp8 (W8A16) or 16-bit ``w``
+(``csrc/gemm/gemm_skinny_a16.hip``).
 """
 
 from __future__ import annotations
@@ -1265,3 +1268,181 @@ def gemm_skinny_grouped(a, w, offsets, out=None, *, a_scale, w_scale, out_dtype=
                       out_quant=out_quant, out_scale=out_scale)
     return _run_skinny(t, a, w, offsets, out, a_scale, w_scale, act, workspace, stream, glu,
                        out_quant, out_scale)
+
+
+# ---------------------------------------------------------------- skinny-M GEMM, 16-bit activations
+# The A16 family (csrc/gemm/gemm_skinny_a16.hip): weight form -> (K elements per 128-byte K-tile of
+# w, the alignment of w_scale; 0: no scales).
+_A16_FORMS = {"mxfp4": (256, 8), "mx": (128, 4), "same": (64, 0)}
+
+
+def _check_skinny_a16(a, w, offsets=None, out=None, *, w_scale=None, out_dtype=None,
+                      act: str = "none", ksplit="auto", workspace=None, grouped: bool = False,
+                      glu: bool = False):
+    """Every refusal of the A16 skinny GEMMs, on the host and before anything is loaded or launched
+    (CPU tensors pass through it; the offsets' content is never read). Returns
+    ``(M, N, K, E, output dtype, S)`` as :func:`_check_skinny` does: ``K`` in elements, ``N`` the
+    rows of ``w``, ``E = 0`` for the dense form, ``S`` the number of K-slices of ``w``'s K-tiles
+    (256 fp4, 128 fp8 or 64 16-bit elements)."""
+    import torch
+
+    what = "the grouped A16 skinny GEMM" if grouped else "the A16 skinny GEMM"
+    if act not in ACTS:
+        raise ValueError(f"unknown activation {act!r}")
+    wd = 3 if grouped else 2
+    if not isinstance(a, torch.Tensor) or not isinstance(w, torch.Tensor) or a.dim() != 2 \
+            or w.dim() != wd:
+        raise ValueError(f"{what} takes a as [M, K] and w as "
+                         f"{'[E, N, K]' if grouped else '[N, K]'}, not "
+                         f"{tuple(getattr(a, 'shape', ()))} and {tuple(getattr(w, 'shape', ()))}")
+    if a.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"{what} takes bf16 or f16 activations, not {a.dtype} (block-scaled "
+                        "activations: gemm_skinny)")
+    form = "mxfp4" if _is_fp4(w) else "mx" if w.dtype == torch.float8_e4m3fn else "same"
+    if form == "same" and w.dtype != a.dtype:
+        raise TypeError(f"{what} takes w as float4_e2m1fn_x2, float8_e4m3fn or a's own "
+                        f"{a.dtype}, not {w.dtype}")
+    kmod, sal = _A16_FORMS[form]
+    M, N, K = a.shape[0], w.shape[-2], a.shape[1]
+    if K != (2 if form == "mxfp4" else 1) * w.shape[-1]:
+        raise ValueError(f"K mismatch: A {tuple(a.shape)} vs W {tuple(w.shape)}"
+                         f"{' (two elements per byte)' if form == 'mxfp4' else ''}")
+    if (w_scale is not None) != (form != "same"):
+        raise ValueError(f"{what} needs w_scale for MX weights and only for them (w is {w.dtype})")
+    if w.device != a.device:
+        raise ValueError("operands on different devices")
+    E = w.shape[0] if grouped else 0
+    if N < 1:
+        raise ValueError(f"{what} needs N >= 1")
+    _check_32_bits(M, N, K)
+    if K < 1 or K % kmod:
+        raise ValueError(f"{what} needs K % {kmod} == 0 for {w.dtype} weights (K = {K})")
+    if grouped:
+        if not 1 <= E <= MAX_GROUPS:
+            raise ValueError(f"{what} takes 1 .. {MAX_GROUPS} groups, not {E}")
+        _check_offsets_dtype(offsets)
+        if offsets.dim() != 1 or offsets.shape[0] != E + 1 or not offsets.is_contiguous():
+            raise ValueError(f"offsets must be contiguous with shape ({E + 1},) for {E} groups, "
+                             f"not {tuple(offsets.shape)}")
+        if offsets.device != a.device:
+            raise ValueError(f"offsets is on {offsets.device}, the operands on {a.device}")
+        if E > 1 and w.stride(0) < N * w.stride(1):
+            raise ValueError(f"w needs experts at least N rows apart (strides "
+                             f"{tuple(w.stride())})")
+        if w.stride(0) * w.element_size() % 16:
+            raise ValueError("the experts' weights must be a multiple of 16 bytes apart")
+    for name, t in (("a", a), ("w", w)):
+        if t.stride(-1) != 1 or t.stride(-2) < t.shape[-1]:
+            raise ValueError(f"{name} needs unit inner stride and rows of at least K (strides "
+                             f"{tuple(t.stride())})")
+        if t.data_ptr() % 16 or t.stride(-2) * t.element_size() % 16:
+            raise ValueError(f"{what} needs 16-byte-aligned rows of {name}")
+    if sal:
+        shape = ((E,) if grouped else ()) + (N, K // 32)
+        if not isinstance(w_scale, torch.Tensor) or w_scale.dtype != torch.uint8:
+            raise TypeError("w_scale must be a uint8 tensor of E8M0 bytes")
+        if w_scale.device != a.device:
+            raise ValueError(f"w_scale is on {w_scale.device}, the operands on {a.device}")
+        if tuple(w_scale.shape) != shape:
+            raise ValueError(f"w_scale must have shape {shape}, not {tuple(w_scale.shape)}")
+        st = w_scale.stride()
+        if st[-1] != 1 or st[-2] % sal or st[-2] < K // 32 or w_scale.data_ptr() % sal or \
+                (grouped and (st[0] % sal or (E > 1 and st[0] < N * st[1]))):
+            raise ValueError(f"w_scale needs unit inner stride, {sal}-byte-aligned rows of at "
+                             f"least K / 32 bytes and a {sal}-byte-aligned base (strides {st})")
+        if max(E, 1) * N * st[-2] >= 2 ** 31:
+            raise ValueError("w_scale spans 2 GiB or more")
+    cols = N // 2 if glu else N
+    if glu and N % (2 * GLU_GROUP):
+        raise ValueError(f"{what} with glu=True needs N % {2 * GLU_GROUP} == 0 (N = {N})")
+    odt = _check_dense_out(what, a, out, out_dtype, (a.dtype, torch.float32), M, cols)
+    nk = K // kmod
+    if ksplit == "auto":
+        S = skinny_auto_slices(skinny_strips(N), nk, max(E, 1))
+    elif isinstance(ksplit, bool) or not isinstance(ksplit, int) or not 1 <= ksplit <= nk:
+        raise ValueError(f"ksplit must be 'auto' or an int in 1 .. {nk} (the K-tiles), not "
+                         f"{ksplit!r}")
+    else:
+        S = ksplit
+    if workspace is not None:
+        if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.float32:
+            raise TypeError(f"workspace must be a float32 tensor, not "
+                            f"{getattr(workspace, 'dtype', type(workspace))}")
+        if workspace.device != a.device:
+            raise ValueError(f"workspace is on {workspace.device}, the operands on {a.device}")
+        need = skinny_workspace_floats(S, M, N)
+        if not workspace.is_contiguous() or workspace.numel() < need or workspace.data_ptr() % 16:
+            raise ValueError(f"workspace must be contiguous, 16-byte aligned and hold at least "
+                             f"{need} floats ({S} slices x {M} x {N}), not {workspace.numel()}")
+    return M, N, K, E, odt, S
+
+
+def _run_skinny_a16(t, a, w, offsets, out, w_scale, act, workspace, stream, glu):
+    """The launch of both A16 forms, after every refusal of :func:`_check_skinny_a16` (``t``)."""
+    import torch
+
+    M, N, K, E, odt, S = t
+    C = load()
+    if a.device.type != "cuda":
+        raise ValueError("native GEMM operands must be ROCm device tensors")
+    if out is None:
+        out = torch.empty((M, N // 2 if glu else N), dtype=odt, device=a.device)
+    if S > 1 and workspace is None:
+        workspace = torch.empty(skinny_workspace_floats(S, M, N), dtype=torch.float32,
+                                device=a.device)
+    fp4, mx = _is_fp4(w), w_scale is not None
+    wm = 2 if fp4 else 1
+    s = _stream(stream, a)
+    C.gemm_skinny_a16(
+        a=a.data_ptr(), w=w.data_ptr(), c=out.data_ptr(), lda=a.stride(0), ldw=wm * w.stride(-2),
+        ldc=out.stride(0), M=M, N=N, K=K, din=dtype_code(a.dtype), dout=dtype_code(odt),
+        dw=DT_FP4 if fp4 else DT_FP8 if mx else -1, w_scale=w_scale.data_ptr() if mx else 0,
+        w_scale_ld=w_scale.stride(-2) if mx else 0, act=ACTS[act], ksplit=S,
+        ws=workspace.data_ptr() if S > 1 else 0, offs=offsets.data_ptr() if E else 0, ngroups=E,
+        w_gstride=wm * w.stride(0) if E else 0,
+        w_scale_gstride=w_scale.stride(0) if E and mx else 0, stream=s, glu=int(bool(glu)))
+    if stream is not None:  # what was allocated here stays allocated until that stream is done
+        out.record_stream(torch.cuda.ExternalStream(s))
+        if S > 1:
+            workspace.record_stream(torch.cuda.ExternalStream(s))
+    return out
+
+
+def gemm_skinny_a16(a, w, out=None, *, w_scale=None, out_dtype=None, act: str = "none",
+                    ksplit="auto", workspace=None, stream=None, glu: bool = False):
+    """``out = act(a @ w.T)`` at decode shapes (``M <= 64``) for bf16 / f16 ``a [M, K]`` that is
+    not quantised, on the weight-streaming split-K kernel ``csrc/gemm/gemm_skinny_a16.hip``.
+    ``w [N, K]`` is one of
+
+    * MXFP4, ``float4_e2m1fn_x2 [N, K / 2]`` with E8M0 ``w_scale [N, K / 32]`` (8-byte aligned),
+      ``K % 256 == 0``: W4A16;
+    * MX-fp8, ``float8_e4m3fn [N, K]`` with ``w_scale`` (4-byte aligned), ``K % 128 == 0``: W8A16;
+    * ``a``'s own dtype, no ``w_scale``, ``K % 64 == 0``.
+
+    The weight bytes are streamed as stored and expanded in registers: the value multiplied is
+    ``e * 2^(s - 127)`` converted to ``a``'s dtype, which is exact whenever it is zero or a normal
+    number of that dtype (every E2M1 / e4m3 element fits the mantissa), the products are summed
+    in f32 and rounded once. The reference is ``act(a.double() @ dequantize(w, w_scale).T)``.
+    Outside that range the result is the conversion instruction's: a scale that pushes a weight
+    past the dtype's largest number, into its subnormals, or the scale byte 0 (not measured for
+    any of the three; the tests stay inside the range). A scale byte 255 makes exactly that weight
+    row's output column NaN, an e4m3 NaN byte too; NaN / Inf in ``a`` reach their output row.
+
+    Output ``a``'s dtype (default) or f32, dense only. ``act``, ``ksplit``, ``workspace``, ``glu``
+    (``w`` in the :func:`pack_glu` layout, ``N % 64 == 0``, ``N / 2`` columns) and the bit-equal
+    repeatability are :func:`gemm_skinny`'s; a K-tile is 128 bytes of a row of ``w``.
+    :func:`_check_skinny_a16` holds every refusal."""
+    t = _check_skinny_a16(a, w, None, out, w_scale=w_scale, out_dtype=out_dtype, act=act,
+                          ksplit=ksplit, workspace=workspace, glu=glu)
+    return _run_skinny_a16(t, a, w, None, out, w_scale, act, workspace, stream, glu)
+
+
+def gemm_skinny_a16_grouped(a, w, offsets, out=None, *, w_scale=None, out_dtype=None,
+                            act: str = "none", ksplit="auto", workspace=None, stream=None,
+                            glu: bool = False):
+    """:func:`gemm_skinny_a16` over per-expert weights ``w [E, N, K]`` (``w_scale
+    [E, N, K / 32]``) in one launch: ``offsets``, the rows written and the equality with the dense
+    form per group are :func:`gemm_skinny_grouped`'s."""
+    t = _check_skinny_a16(a, w, offsets, out, w_scale=w_scale, out_dtype=out_dtype, act=act,
+                          ksplit=ksplit, workspace=workspace, grouped=True, glu=glu)
+    return _run_skinny_a16(t, a, w, offsets, out, w_scale, act, workspace, stream, glu)
