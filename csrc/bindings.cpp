@@ -16,6 +16,7 @@
 #include "comm/comm.h"
 #include "gemm/gemm.h"
 #include "gemm/gemm_skinny.h"
+#include "gemm/gemm_w4a8.h"
 #include "gemm/glu_act.h"
 #include "moe/moe.h"
 #include "moe/moe_route_map.h"
@@ -294,6 +295,31 @@ PYBIND11_MODULE(_C, m) {
         py::arg("ksplit") = 0, py::arg("ws") = 0, py::arg("offs") = 0, py::arg("ngroups") = 0,
         py::arg("w_gstride") = 0, py::arg("w_scale_gstride") = 0, py::arg("stream") = 0,
         py::arg("glu") = 0);
+  // Tiled W4A8 GEMM (gemm_w4a8.h): a e4m3 [M, K], w E2M1 pairs [N, K / 2] (ldw / w_gstride in fp4
+  // elements), dense or (dout = DT_FP8 with c_scale) MX-fp8 output; grouped with offs / ngroups as
+  // gemm_grouped takes them. Not routed through gemm_launch.
+  m.attr("W4A8_STAGES") = kW4A8Stages;
+  m.def("gemm_w4a8",
+        [](uintptr_t a, uintptr_t w, uintptr_t c, int64_t lda, int64_t ldw, int64_t ldc, int M,
+           int N, int K, int dout, int tile, uintptr_t a_scale, uintptr_t w_scale,
+           int64_t a_scale_ld, int64_t w_scale_ld, int act, int glu, uintptr_t c_scale,
+           int64_t c_scale_ld, uintptr_t offs, int ngroups, int64_t w_gstride,
+           int64_t w_scale_gstride, uintptr_t stream) {
+          GemmArgs g = make_args(a, w, c, lda, ldw, ldc, M, N, K, 0, 0, 0, 0);
+          set_scales_epilogue(g, a_scale, w_scale, a_scale_ld, w_scale_ld, c_scale, c_scale_ld,
+                              act, glu);
+          g.grp_offs = (const int*)offs;
+          g.ngroups = ngroups;
+          g.b_gstride = w_gstride;
+          g.b_scale_gstride = w_scale_gstride;
+          check(gemm_w4a8_launch(g, dout, tile, (hipStream_t)stream), "gemm_w4a8");
+        },
+        py::arg("a"), py::arg("w"), py::arg("c"), py::arg("lda"), py::arg("ldw"), py::arg("ldc"),
+        py::arg("M"), py::arg("N"), py::arg("K"), py::arg("dout"), py::arg("tile") = 0,
+        py::arg("a_scale") = 0, py::arg("w_scale") = 0, py::arg("a_scale_ld") = 0,
+        py::arg("w_scale_ld") = 0, py::arg("act") = 0, py::arg("glu") = 0, py::arg("c_scale") = 0,
+        py::arg("c_scale_ld") = 0, py::arg("offs") = 0, py::arg("ngroups") = 0,
+        py::arg("w_gstride") = 0, py::arg("w_scale_gstride") = 0, py::arg("stream") = 0);
   // the launch arithmetic of gemm_skinny.h: (strips, the automatic slice count)
   m.def("skinny_plan", [](int N, int nk, int groups, int cus) {
     const int strips = skinny_strips(N);

@@ -20,10 +20,15 @@ fc1 runs with ``glu=True``, so the product is formed in the GEMM's epilogue and 
 ``act`` only, straight into fc2. ``fused=False`` there is the chain the fused epilogue replaces
 (gated: f32 fc1, ``ops.glu.glu``, the row quantiser; else bf16 fc1 and the row quantiser).
 
-``fmt="w4a8"`` (``kernel="skinny"`` only) keeps the weights in MXFP4 and the activations in
+``fmt="w4a8"`` (``kernel="skinny"``, or ``"mixed"`` below) keeps the weights in MXFP4 and the activations in
 MX-fp8: ``X`` is quantised with ``quantize_mx``, fc1 writes MX-fp8 (``out_quant="mx"``), and both
 layers run ``gemm_skinny``'s mixed pair, so they stream the fp4 bytes and only the weights pay
 the 4-bit error.
+
+``kernel="mixed"`` (``fmt="w4a8"`` only, any ``seq``: prefill) runs the same chain on the tiled
+W4A8 kernel, ``ops.gemm.gemm_w4a8``: fc1 with ``act`` / ``glu`` and ``out_quant="mx"``, then
+fc2. ``fused=False`` there is bf16 fc1 and the row quantiser (gated: f32 fc1, ``ops.glu.glu``,
+the row quantiser).
 
 ``fmt="w4a16"`` / ``"w8a16"`` (``kernel="skinny"`` only) is weight-only quantisation: MXFP4 /
 MX-fp8 weights, ``X`` and ``H`` stay 16-bit and nothing is quantised per forward. Both layers run
@@ -40,7 +45,7 @@ from __future__ import annotations
 
 FMTS = ("mx", "mxfp4", "w4a8", "w4a16", "w8a16")
 A16 = "a16"  # the activation "format" of the weight-only formats: not quantised
-KERNELS = ("tiled", "skinny")
+KERNELS = ("tiled", "skinny", "mixed")
 SKINNY_ROWS = 64  # the rows one pass over the weights serves (gemm_skinny)
 
 
@@ -68,10 +73,15 @@ def _check_fmt_kernel(fmt: str, kernel: str) -> int:
     """The format's refusals that the models share; returns what hidden and ffn are multiples
     of (the K-tile of the narrower operand)."""
     afmt, wfmt = _fmt_pair(fmt)
-    if afmt != wfmt and kernel != "skinny":
+    if kernel == "mixed":
+        if fmt != "w4a8":
+            raise ValueError(f"kernel='mixed' is the tiled W4A8 GEMM: it takes fmt='w4a8' only, "
+                             f"not fmt={fmt!r}")
+    elif afmt != wfmt and kernel != "skinny":
         raise ValueError(f"fmt={fmt!r} needs kernel='skinny': only the skinny GEMMs multiply "
                          "MX-fp8 or 16-bit activations by narrower MX weights, the tiled kernel "
-                         "takes one format for both operands")
+                         "takes one format for both operands (fmt='w4a8' also runs at any seq "
+                         "with kernel='mixed', the tiled W4A8 GEMM)")
     return 256 if wfmt == "mxfp4" else 128
 
 
@@ -145,6 +155,8 @@ class MxMLP:
         glu = {"glu": True} if self.gated else {}
         if self.kernel == "skinny":
             return self._forward_skinny(xq, xs)
+        if self.kernel == "mixed":
+            return self._forward_mixed(xq, xs)
         if self.fused:
             hq, hs = gemm(xq, self.w1q, a_scale=xs, w_scale=self.w1s, act=self.act,
                           tile=self.tile, out_quant=self.fmt, **glu)
@@ -173,6 +185,25 @@ class MxMLP:
         else:
             hq, hs = quant(gemm_skinny(xq, self.w1q, act=self.act, **fc1))
         gemm_skinny(hq, self.w2q, self.out, a_scale=hs, w_scale=self.w2s)
+        return self.out
+
+    def _forward_mixed(self, xq, xs):
+        import torch
+
+        from ddlb_amd.ops.gemm import gemm_w4a8
+        from ddlb_amd.ops.mx import quantize_mx
+
+        fc1 = dict(a_scale=xs, w_scale=self.w1s, tile=self.tile)
+        if self.fused:
+            hq, hs = gemm_w4a8(xq, self.w1q, act=self.act, glu=self.gated, out_quant="mx", **fc1)
+        elif self.gated:
+            from ddlb_amd.ops.glu import glu
+
+            hq, hs = quantize_mx(glu(gemm_w4a8(xq, self.w1q, out_dtype=torch.float32, **fc1),
+                                     self.act))
+        else:
+            hq, hs = quantize_mx(gemm_w4a8(xq, self.w1q, act=self.act, **fc1))
+        gemm_w4a8(hq, self.w2q, self.out, a_scale=hs, w_scale=self.w2s, tile=self.tile)
         return self.out
 
     @staticmethod

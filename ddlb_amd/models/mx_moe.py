@@ -39,8 +39,11 @@ goes between it and fc2; ``fused=False`` is the chain the fused epilogue replace
     Hq, sH = quantise(H)             the row quantiser
     Yp = Hq W2[e].T                  bf16
 
-``fmt="w4a8"`` (``kernel="skinny"`` only): MXFP4 weights under MX-fp8 activations, as
+``fmt="w4a8"`` (``kernel="skinny"``, or ``"mixed"`` below): MXFP4 weights under MX-fp8 activations, as
 :class:`MxMLP` describes it; fc1 writes MX-fp8, so fc2 is the mixed pair too.
+
+``kernel="mixed"`` (``fmt="w4a8"`` only, any number of tokens: prefill) runs both layers on the
+tiled W4A8 kernel, ``ops.gemm.gemm_w4a8_grouped``, with either dispatch; ``fused`` as above.
 
 ``fmt="w4a16"`` / ``"w8a16"`` (``kernel="skinny"`` only): weight-only quantisation. The routed
 rows stay bf16 (``ops.moe.gather``, or ``index_select`` with the torch dispatch) and both layers
@@ -94,7 +97,7 @@ def expert_ids_topk(seq: int, experts: int, k: int, seed: int = 0):
 
 
 DISPATCHES = ("torch", "native")
-KERNELS = ("tiled", "skinny")
+KERNELS = ("tiled", "skinny", "mixed")
 
 
 class MxMoE:
@@ -197,7 +200,19 @@ class MxMoE:
         else:
             perm, offsets = self.route()
             xq, xs = quant(self.X.index_select(0, perm))
-        if self.kernel == "skinny" and self.fused:
+        if self.kernel == "mixed":
+            from ddlb_amd.ops.gemm import gemm_w4a8_grouped
+
+            fc1 = dict(a_scale=xs, w_scale=self.w1s, tile=self.tile)
+            if self.fused:
+                hq, hs = gemm_w4a8_grouped(xq, self.w1q, offsets, act=self.act, glu=True,
+                                           out_quant="mx", **fc1)
+            else:
+                from ddlb_amd.ops.glu import glu
+
+                c = gemm_w4a8_grouped(xq, self.w1q, offsets, out_dtype=torch.float32, **fc1)
+                hq, hs = quant(glu(c, self.act))
+        elif self.kernel == "skinny" and self.fused:
             from ddlb_amd.ops.gemm import gemm_skinny_grouped
 
             hq, hs = gemm_skinny_grouped(xq, self.w1q, offsets, a_scale=xs, w_scale=self.w1s,
@@ -216,7 +231,10 @@ class MxMoE:
             h = gemm_grouped(xq, self.w1q, offsets, a_scale=xs, w_scale=self.w1s, act=self.act,
                              tile=self.tile, glu=True, out_dtype=torch.bfloat16)
             hq, hs = quant(h)
-        if self.kernel == "skinny":
+        if self.kernel == "mixed":
+            gemm_w4a8_grouped(hq, self.w2q, offsets, self.ysorted, a_scale=hs, w_scale=self.w2s,
+                              tile=self.tile)
+        elif self.kernel == "skinny":
             gemm_skinny_grouped(hq, self.w2q, offsets, self.ysorted, a_scale=hs,
                                 w_scale=self.w2s)
         else:

@@ -24,6 +24,9 @@ decode shapes (``M`` or the rows per expert ``<= 64``) on the weight-streaming s
 ``gemm_skinny_a16(a, w)`` / ``gemm_skinny_a16_grouped(a, w, offsets)``: the same shapes for bf16 /
 f16 ``a`` that is not quantised, on MXFP4 (W4A16), MX-fp8 (W8A16) or 16-bit ``w``
 (``csrc/gemm/gemm_skinny_a16.hip``).
+``gemm_w4a8(a, w)`` / ``gemm_w4a8_grouped(a, w, offsets)``: MX-fp8 ``a`` on MXFP4 ``w`` at prefill
+shapes, any ``M``, on the tiled W4A8 kernel (``csrc/gemm/gemm_w4a8_kernels.h``), with ``act``,
+``glu`` and ``out_quant="mx"``; ``gemm()`` and ``gemm_grouped()`` keep refusing mixed dtypes.
 """
 
 from __future__ import annotations
@@ -1446,3 +1449,170 @@ def gemm_skinny_a16_grouped(a, w, offsets, out=None, *, w_scale=None, out_dtype=
     t = _check_skinny_a16(a, w, offsets, out, w_scale=w_scale, out_dtype=out_dtype, act=act,
                           ksplit=ksplit, workspace=workspace, grouped=True, glu=glu)
     return _run_skinny_a16(t, a, w, offsets, out, w_scale, act, workspace, stream, glu)
+
+
+# ---------------------------------------------------------------- tiled W4A8 GEMM (prefill shapes)
+# MX-fp8 a on MXFP4 w on a tiled kernel of its own (csrc/gemm/gemm_w4a8_kernels.h). Both scale
+# arrays are read one 32-bit word per row and K-tile: 4-byte alignment for w_scale too.
+W4A8_TILES = ("256x128", "128x128")  # gemm_w4a8.h w4a8_offers()
+_MX_W4A8_TILED = _ScaledFormat(1, 256, 4, W4A8_TILES, "the W4A8 GEMM", False,
+                               "fp8 x fp4 operands", "")
+
+
+def _check_w4a8(a, w, offsets=None, out=None, *, a_scale=None, w_scale=None, out_dtype=None,
+                tile: str = "auto", act: str = "none", glu: bool = False, out_quant=None,
+                out_scale=None, grouped: bool = False):
+    """Every refusal of :func:`gemm_w4a8` / :func:`gemm_w4a8_grouped`, on the host and before
+    anything is loaded or launched (CPU tensors pass through it; the offsets' content is never
+    read). Returns ``(M, N, K, E, output dtype)``: ``K`` in elements, ``N`` the rows of ``w``
+    (the output has ``N / 2`` columns with ``glu``), ``E = 0`` for the dense form; with
+    ``out_quant`` the output dtype is the quantised data's."""
+    import torch
+
+    what = "the grouped W4A8 GEMM" if grouped else "the W4A8 GEMM"
+    if act not in ACTS:
+        raise ValueError(f"unknown activation {act!r}")
+    if out_quant == "mxfp4":
+        raise ValueError(f"{what} has no out_quant='mxfp4': nothing in a W4A8 chain reads MXFP4 "
+                         "activations (out_quant='mx' writes the next layer's MX-fp8 a)")
+    _known_out_quant(out_quant, optional=True)
+    if out_quant is None and out_scale is not None:
+        raise ValueError("out_scale goes with out_quant")
+    wd = 3 if grouped else 2
+    if not isinstance(a, torch.Tensor) or not isinstance(w, torch.Tensor) or a.dim() != 2 \
+            or w.dim() != wd:
+        raise ValueError(f"{what} takes a as [M, K] and w as "
+                         f"{'[E, N, K / 2]' if grouped else '[N, K / 2]'}, not "
+                         f"{tuple(getattr(a, 'shape', ()))} and {tuple(getattr(w, 'shape', ()))}")
+    if a.dtype != torch.float8_e4m3fn or not _is_fp4(w):
+        raise TypeError(f"{what} takes float8_e4m3fn a on float4_e2m1fn_x2 w, not {a.dtype} on "
+                        f"{w.dtype}")
+    if a.shape[1] != 2 * w.shape[-1]:
+        raise ValueError(f"K mismatch: A {tuple(a.shape)} vs W {tuple(w.shape)} (two E2M1 "
+                         "elements per byte)")
+    if a_scale is None or w_scale is None:
+        raise ValueError(f"{what} needs a_scale and w_scale (there is no unit-scale kernel)")
+    if w.device != a.device:
+        raise ValueError("operands on different devices")
+    M, N, K = a.shape[0], w.shape[-2], a.shape[1]
+    E = w.shape[0] if grouped else 0
+    if N < 1:
+        raise ValueError(f"{what} needs N >= 1")
+    _check_32_bits(M, N, K)
+    if grouped:
+        if not 1 <= E <= MAX_GROUPS:
+            raise ValueError(f"{what} takes 1 .. {MAX_GROUPS} groups, not {E}")
+        _check_offsets_dtype(offsets)
+        if offsets.dim() != 1 or offsets.shape[0] != E + 1 or not offsets.is_contiguous():
+            raise ValueError(f"offsets must be contiguous with shape ({E + 1},) for {E} groups, "
+                             f"not {tuple(offsets.shape)}")
+        if offsets.device != a.device:
+            raise ValueError(f"offsets is on {offsets.device}, the operands on {a.device}")
+        if E > 1 and w.stride(0) < N * w.stride(1):
+            raise ValueError(f"w needs experts at least N rows apart (strides "
+                             f"{tuple(w.stride())})")
+        if w.stride(0) % 16:
+            raise ValueError("the experts' weights must be a multiple of 16 bytes apart")
+        if not isinstance(w_scale, torch.Tensor) or w_scale.dim() != 3:
+            raise ValueError(f"w_scale must have shape {(E, N, K // 32)}, not "
+                             f"{tuple(getattr(w_scale, 'shape', ()))}")
+        if w_scale.stride(0) % 4 or (E > 1 and w_scale.stride(0) < N * w_scale.stride(1)):
+            raise ValueError(f"w_scale needs experts a multiple of 4 bytes and at least N rows "
+                             f"apart (strides {tuple(w_scale.stride())})")
+        if (M // 128 + E) * (-(-N // 128)) >= 2 ** 31:
+            raise ValueError(f"{what}: the grid bound does not fit 32 bits")
+    for name, t in (("a", a), ("w", w)):
+        if t.stride(-1) != 1 or t.stride(-2) < t.shape[-1]:
+            raise ValueError(f"{name} needs unit inner stride and rows of at least K (strides "
+                             f"{tuple(t.stride())})")
+        if t.data_ptr() % 16 or t.stride(-2) * t.element_size() % 16:
+            raise ValueError(f"{what} needs 16-byte-aligned rows of {name}")
+    # tile, K % 256 and the scale layout, per expert slice
+    for g in sorted({0, E - 1}) if grouped else (None,):
+        _check_block_scaled(_MX_W4A8_TILED, a, w if g is None else w[g], a_scale,
+                            w_scale if g is None else w_scale[g], M, tile, "auto", 0, 0)
+    # the output: N columns, or N / 2 from whole 64-row gate / up groups; quantised in whole
+    # 32-column blocks, as many as the GEMM that reads them takes per K-tile
+    cols = N // 2 if glu else N
+    nmod = (2 if glu else 1) * (128 if out_quant else GLU_GROUP)
+    if (glu or out_quant) and N % nmod:
+        raise ValueError(f"{what} with glu={bool(glu)}, out_quant={out_quant!r} needs "
+                         f"N % {nmod} == 0 (N = {N})")
+    if out_quant is not None:
+        _check_quant_dtype(out_quant, out_dtype)
+        _check_quant_outputs(a, out, out_scale, out_quant, M, cols)
+        return M, N, K, E, out_quant_dtype(out_quant)
+    odt = _check_dense_out(what, a, out, out_dtype,
+                           (torch.bfloat16, torch.float16, torch.float32), M, cols)
+    return M, N, K, E, odt
+
+
+def _run_w4a8(t, a, w, offsets, out, a_scale, w_scale, tile, act, glu, out_quant, out_scale,
+              stream):
+    """The launch of both W4A8 forms, after every refusal of :func:`_check_w4a8` (``t``)."""
+    import torch
+
+    M, N, K, E, odt = t
+    C = load()
+    if a.device.type != "cuda":
+        raise ValueError("native GEMM operands must be ROCm device tensors")
+    cols = N // 2 if glu else N
+    if out is None:
+        out = torch.empty((M, cols), dtype=odt, device=a.device)
+    if out_quant is not None and out_scale is None:
+        out_scale = torch.empty((M, cols // 32), dtype=torch.uint8, device=a.device)
+    s = _stream(stream, a)
+    C.gemm_w4a8(
+        a=a.data_ptr(), w=w.data_ptr(), c=out.data_ptr(), lda=a.stride(0), ldw=2 * w.stride(-2),
+        ldc=out.stride(0), M=M, N=N, K=K, dout=DT_FP8 if out_quant else dtype_code(odt),
+        tile=TILES[tile], a_scale=a_scale.data_ptr(), w_scale=w_scale.data_ptr(),
+        a_scale_ld=a_scale.stride(0), w_scale_ld=w_scale.stride(-2), act=ACTS[act],
+        glu=int(bool(glu)), c_scale=out_scale.data_ptr() if out_quant else 0,
+        c_scale_ld=out_scale.stride(0) if out_quant else 0,
+        offs=offsets.data_ptr() if E else 0, ngroups=E, w_gstride=2 * w.stride(0) if E else 0,
+        w_scale_gstride=w_scale.stride(0) if E else 0, stream=s)
+    if stream is not None:  # what was allocated here stays allocated until that stream is done
+        out.record_stream(torch.cuda.ExternalStream(s))
+        if out_quant is not None:
+            out_scale.record_stream(torch.cuda.ExternalStream(s))
+    return out if out_quant is None else (out[:M], out_scale[:M])
+
+
+def gemm_w4a8(a, w, out=None, *, a_scale, w_scale, out_dtype=None, tile: str = "auto",
+              act: str = "none", glu: bool = False, out_quant=None, out_scale=None, stream=None):
+    """``out = act(a @ w.T)`` for MX-fp8 ``a [M, K]`` (float8_e4m3fn) on MXFP4 ``w [N, K / 2]``
+    (float4_e2m1fn_x2) at prefill shapes, any ``M``, on the tiled W4A8 kernel
+    (``csrc/gemm/gemm_w4a8_kernels.h``): one mixed-format block-scaled MFMA per 128 K elements,
+    the fp4 form's weight bytes with 8-bit activations. ``K % 256 == 0``; ``a_scale [M, K / 32]``
+    and ``w_scale [N, K / 32]`` E8M0 bytes, both 4-byte aligned; operand rows 16-byte aligned.
+    Output bf16 (default) / f16 / f32 on any row pitch, any ``N >= 1``. The decode sibling
+    is :func:`gemm_skinny` (``M <= 64``); :func:`gemm` keeps refusing mixed dtypes.
+
+    ``tile``: ``"auto"`` or one of :data:`W4A8_TILES`. ``act`` applies to the f32 sum before the one
+    rounding. ``glu=True``: ``w`` is the :func:`pack_glu` weight, ``N % 64 == 0``, and the output
+    has ``N / 2`` columns, ``act(gate) * up`` in f32 (:func:`glu_reference`). ``out_quant="mx"``:
+    the result leaves as MX-fp8 data and E8M0 scales per 32 output columns, ``(q, s)``, the next
+    ``gemm_w4a8``'s ``a`` / ``a_scale`` (output columns ``% 128 == 0``; ``out`` / ``out_scale`` are
+    used when given). ``out_quant="mxfp4"`` is refused: nothing in a W4A8 chain reads it.
+    :func:`_check_w4a8` holds every refusal."""
+    t = _check_w4a8(a, w, None, out, a_scale=a_scale, w_scale=w_scale, out_dtype=out_dtype,
+                    tile=tile, act=act, glu=glu, out_quant=out_quant, out_scale=out_scale)
+    return _run_w4a8(t, a, w, None, out, a_scale, w_scale, tile, act, glu, out_quant, out_scale,
+                     stream)
+
+
+def gemm_w4a8_grouped(a, w, offsets, out=None, *, a_scale, w_scale, out_dtype=None,
+                      tile: str = "auto", act: str = "none", glu: bool = False, out_quant=None,
+                      out_scale=None, stream=None):
+    """:func:`gemm_w4a8` over per-expert weights in one launch (MoE prefill): rows
+    ``[o'[g], o'[g + 1])`` of ``a [T, K]`` times ``w[g]`` of ``w [E, N, K / 2]`` under
+    ``w_scale [E, N, K / 32]``. ``offsets`` is the int32 ``[E + 1]`` device tensor of
+    :func:`gemm_grouped`, read and clamped by the kernel only (:func:`clamp_offsets`; no host
+    sync); empty groups are legal, rows outside ``[o'[0], o'[E])`` are not written (of
+    ``out_scale`` neither), and a group's rows are bit for bit what :func:`gemm_w4a8` writes for
+    them with the same tile code."""
+    t = _check_w4a8(a, w, offsets, out, a_scale=a_scale, w_scale=w_scale, out_dtype=out_dtype,
+                    tile=tile, act=act, glu=glu, out_quant=out_quant, out_scale=out_scale,
+                    grouped=True)
+    return _run_w4a8(t, a, w, offsets, out, a_scale, w_scale, tile, act, glu, out_quant,
+                     out_scale, stream)
