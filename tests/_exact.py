@@ -419,3 +419,232 @@ def gate_ld(pred, align, hi=2 ** 40):
 def align_of(nbytes, esz):
     """Elements per ``nbytes`` bytes (the leading-dimension step that keeps rows so aligned)."""
     return nbytes // math.gcd(nbytes, esz)
+
+
+# ---------------------------------------------------------------------------- code points
+E2M1_MAG = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)   # codes 0..7; codes 8..15 are their negatives
+CODE_K = 256                                           # K of the code cases: 8 blocks
+
+
+def e2m1_values():
+    """The 16 E2M1 codes as float64 (``sign << 3 | code``; code 8 is -0)."""
+    mag = torch.tensor(E2M1_MAG, dtype=torch.float64)
+    return torch.cat([mag, -mag])
+
+
+def e4m3_values():
+    """The 256 e4m3fn bytes as float64 (torch's own cast; NaN at 0x7F and 0xFF)."""
+    return torch.arange(256, dtype=torch.int32).to(torch.uint8).view(FP8).to(torch.float32).double()
+
+
+def pack_nibbles(nib):
+    """Integer nibbles ``[R, K]`` -> bytes ``[R, K / 2]``, element ``2j`` in the low nibble."""
+    n = nib.to(torch.int32).reshape(nib.shape[0], -1, 2)
+    return (n[..., 0] | (n[..., 1] << 4)).to(torch.uint8)
+
+
+def unpack_nibbles(b):
+    return torch.stack((b & 0xF, b >> 4), dim=2).reshape(b.shape[0], -1).to(torch.int64)
+
+
+def ints_as_e2m1(x):
+    """Integers in -3..3 (any float dtype) as packed E2M1 bytes."""
+    v = x.to(torch.float32)
+    code = torch.tensor((0, 2, 4, 5), device=v.device)[v.abs().long()]
+    return pack_nibbles(code | ((v < 0).long() << 3))
+
+
+def decode64(data, s, fmt):
+    """``data`` (e4m3 bytes ``[R, K]``, or E2M1 byte pairs ``[R, K / 2]``) under the E8M0 bytes
+    ``s [R, K / 32]`` as float64, decoded by table."""
+    if fmt == "e2m1":
+        v = e2m1_values()[unpack_nibbles(data.view(torch.uint8))]
+    else:
+        v = e4m3_values()[data.view(torch.uint8).long()]
+    R, K = v.shape
+    return (v.reshape(R, K // BLOCK, BLOCK) * pow2_f64(s.to(torch.int64) - 127).unsqueeze(2)) \
+        .reshape(R, K)
+
+
+def code_pos(r, nb=CODE_K // BLOCK):
+    """The K position of row ``r``'s code: ``r mod 32`` within block ``(r // 32 + r) mod nb``, a
+    different block from one row to the next and a different position for every ``r < 32 nb``."""
+    return ((r // 32 + r) % nb) * BLOCK + r % BLOCK
+
+
+def code_case(fmt, K=CODE_K):
+    """The every-code operand of ``tests/test_gemm_codes_gpu.py``, on the CPU:
+    ``(data, s, pos, neg0)``. ``"e4m3"``: rows are the 254 finite bytes in order, ``data`` uint8
+    ``[254, K]``, zero but for byte ``codes[r]`` at ``pos[r]``. ``"e2m1"``: 32 rows, row
+    ``r = 2 c + h`` holds code ``c`` at ``pos[r]`` (odd ``h``: the high nibble) and in the other
+    nibble of that byte a different non-zero code; ``data`` uint8 ``[32, K / 2]``. ``s[r, j] =
+    125 + (r + j) mod 5``: neighbouring blocks differ. ``neg0``: the rows whose code is -0."""
+    nb = K // BLOCK
+    if fmt == "e4m3":
+        codes = torch.tensor([c for c in range(256) if c not in (0x7F, 0xFF)])
+        R = codes.numel()
+        assert R <= 32 * nb
+        pos = torch.tensor([code_pos(r, nb) for r in range(R)])
+        data = torch.zeros((R, K), dtype=torch.uint8)
+        data[torch.arange(R), pos] = codes.to(torch.uint8)
+        neg0 = codes == 0x80
+    else:
+        R = 32
+        pos = torch.tensor([code_pos(r, nb) for r in range(R)])
+        codes = torch.arange(R) // 2
+        nib = torch.zeros((R, K), dtype=torch.int64)
+        nib[torch.arange(R), pos] = codes
+        nib[torch.arange(R), pos ^ 1] = torch.where(codes == 5, 3, 5)
+        assert bool((pos % 2 == torch.arange(R) % 2).all())
+        data = pack_nibbles(nib)
+        neg0 = codes == 8
+    assert int(torch.unique(pos).numel()) == R
+    blk = pos // BLOCK
+    assert bool((blk[1:] != blk[:-1]).all())
+    s = (125 + (torch.arange(R).unsqueeze(1) + torch.arange(nb).unsqueeze(0)) % 5).to(torch.uint8)
+    return data, s, pos, neg0
+
+
+def one_hot(pos, K):
+    """float64 ``[R, K]`` with 1.0 at ``pos[r]`` of row ``r``: the identity partner."""
+    p = torch.zeros((pos.numel(), K), dtype=torch.float64)
+    p[torch.arange(pos.numel()), pos] = 1.0
+    return p
+
+
+def same_bits(got, want64, by_value=None):
+    """``got`` (f32) equals the fp64 ``want64`` bit for bit as int32; the elements of the mask
+    ``by_value`` (a -0 operand: its product is ADDED to a +0 accumulator, which IEEE 754 makes +0
+    in every kernel) are compared by value."""
+    want = want64.to(torch.float32)
+    assert torch.equal(want.double(), want64), "the reference is no exact f32"
+    g, w = got.contiguous().view(torch.int32).clone(), (want + 0.0).view(torch.int32)
+    if by_value is not None:
+        assert bool((got[by_value] == want[by_value]).all())
+        g[by_value] = w[by_value]
+    bad = (g != w).nonzero()
+    assert bad.numel() == 0, f"{bad.shape[0]} elements differ, the first at {bad[:8].tolist()}"
+
+
+# ---------------------------------------------------------------------------- the A16 range
+A16_BLOCKS = 64       # blocks (rows of ``a``) per launch of the range test
+
+
+def a16_range_mask(fmt, dtype):
+    """The documented exact range of ``gemm_skinny_a16``, as a plain fp64 predicate: bool
+    ``[codes, 256]`` over (code, scale byte), true where ``decode(code) * 2^(s - 127)`` is zero or
+    a normal number of ``dtype``, for the finite codes and the scale bytes 1..254."""
+    vals = e4m3_values() if fmt == "mx" else e2m1_values()
+    fin = torch.isfinite(vals)
+    v = torch.where(fin, vals, 0.0).unsqueeze(1) * pow2_f64(torch.arange(256) - 127).unsqueeze(0)
+    fi = torch.finfo(dtype)
+    ok = (v == 0) | ((v.abs() >= fi.tiny) & (v.abs() <= fi.max))
+    ok &= fin.unsqueeze(1)
+    ok[:, 0] = ok[:, 255] = False
+    return ok
+
+
+def a16_range_case(fmt, pairs):
+    """``pairs [P, 2]`` (code, scale byte) laid out for one launch: pair ``p`` is block
+    ``p mod 64`` of weight row ``p // 64``, its code at position ``(row + block) mod 32`` of the
+    block, every other element zero; the unused blocks of the last row hold code 0 under byte 127.
+    Returns ``(data uint8, s uint8 [N, 64], want64 [64, N], used bool [64, N])``: with ``a``
+    one-hot per row (1.0 over block ``m``) the output ``[m, n]`` is the weight of pair
+    ``64 n + m``."""
+    P = pairs.shape[0]
+    N, K = -(-P // A16_BLOCKS), A16_BLOCKS * BLOCK
+    code = torch.zeros(N * A16_BLOCKS, dtype=torch.int64)
+    s = torch.full((N * A16_BLOCKS,), 127, dtype=torch.int64)
+    code[:P], s[:P] = pairs[:, 0], pairs[:, 1]
+    code, s = code.reshape(N, A16_BLOCKS), s.reshape(N, A16_BLOCKS)
+    n, b = torch.meshgrid(torch.arange(N), torch.arange(A16_BLOCKS), indexing="ij")
+    elems = torch.zeros((N, K), dtype=torch.int64)
+    elems[n, b * BLOCK + (n + b) % BLOCK] = code
+    data = pack_nibbles(elems) if fmt == "mxfp4" else elems.to(torch.uint8)
+    vals = (e4m3_values() if fmt == "mx" else e2m1_values())[code]
+    want = (vals * pow2_f64(s - 127)).t().contiguous()
+    used = (torch.arange(N * A16_BLOCKS) < P).reshape(N, A16_BLOCKS).t().contiguous()
+    return data, s.to(torch.uint8), want, used
+
+
+# ---------------------------------------------------------------------------- far: three families
+# The skinny GEMMs (block-scaled and A16) and the tiled W4A8 GEMM: (a's form, w's form).
+FAMILIES = {"skinny-mx": ("fp8", "fp8"), "skinny-mxfp4": ("fp4", "fp4"),
+            "skinny-w4a8": ("fp8", "fp4"), "a16-mxfp4": ("a16", "fp4"), "a16-mx": ("a16", "fp8"),
+            "a16-same": ("a16", "same"), "w4a8": ("fp8", "fp4")}
+FAR_K = 512                         # 4 fp8, 2 fp4, 8 16-bit K-tiles: a K-split of 2 everywhere
+SKINNY_PITCH = (80 << 20) + 16      # rows from 26 on lie past 2^31, rows from 52 on past 2^32
+SKINNY_AC, SKINNY_W = (64, 150), (17, 300)   # (M, N) with a or c far; with w far
+FAR_EXPERT = 2 ** 31 + 2 ** 20      # bytes between experts: 1 starts past 2^31, 2 past 2^32
+FAR_EXPERT_SCALES = 2 ** 19         # where w_scale lies behind its expert's w
+GROUP_A_PITCH = {"skinny": (200 << 20) + 16, "w4a8": (48 << 20) + 16}
+
+
+def a16_scale_rows_ok(N, scale_ld, E=0):
+    """The ``w_scale`` gate of ``_check_skinny_a16``."""
+    return max(E, 1) * N * scale_ld < 2 ** 31
+
+
+def far_scale_bytes(rows, K, seed):
+    """E8M0 bytes 125..129 ``[rows, K / 32]``, CPU-drawn, rows pairwise distinct."""
+    g = torch.Generator(device="cpu").manual_seed(seed + 7919 * rows + K)
+    s = (125 + torch.randint(0, 5, (rows, K // BLOCK), generator=g)).to(torch.uint8)
+    assert int(torch.unique(s, dim=0).shape[0]) == rows
+    return s
+
+
+def family_case(fam, M, N, K, dt=torch.bfloat16):
+    """The integer case of a family, on the CPU: ``(a, w, s_a, s_w, ref64)`` with ``a`` / ``w`` as
+    stored (e4m3, packed E2M1 bytes as uint8, or ``dt``), the scale bytes (``None`` where the
+    form has none) and the fp64 product of the dequantised operands."""
+    fa, fw = FAMILIES[fam]
+    a8, w8 = far_operands(M, N, K, FP8)
+    s_a = far_scale_bytes(M, K, 41) if fa != "a16" else None
+    s_w = far_scale_bytes(N, K, 42) if fw != "same" else None
+    unit = lambda r: torch.full((r, K // BLOCK), 127, dtype=torch.uint8)   # noqa: E731
+    ref = exact_scaled(a8, w8, unit(M) if s_a is None else s_a, unit(N) if s_w is None else s_w)
+    assert torch.equal(ref.float().double(), ref)
+    form = {"fp8": lambda x: x, "fp4": ints_as_e2m1, "a16": lambda x: x.float().to(dt),
+            "same": lambda x: x.float().to(dt)}
+    return form[fa](a8), form[fw](w8), s_a, s_w, ref
+
+
+def far_experts(backing, x, ld_bytes, gs_bytes, byte0=0, fill=POISON):
+    """``x [E, N, C]`` as a strided view of ``backing``: rows ``ld_bytes`` and experts
+    ``gs_bytes`` apart, expert 0 at byte ``guard + byte0`` (``fill``: as :func:`far_view`)."""
+    E, N, C = x.shape
+    esz = x.element_size()
+    start = backing.guard + byte0
+    assert ld_bytes % esz == 0 and gs_bytes % esz == 0 and start % 16 == 0
+    assert ld_bytes >= C * esz and gs_bytes >= N * ld_bytes
+    assert start + (E - 1) * gs_bytes + far_span(N, C * esz, ld_bytes) <= backing.numel()
+    if fill is not None:
+        far_fill(backing, fill, x.dtype)
+    typed = backing if _is_raw(x.dtype) else backing.view(x.dtype)
+    view = torch.as_strided(typed, (E, N, C), (gs_bytes // esz, ld_bytes // esz, 1), start // esz)
+    assert view.data_ptr() == backing.data_ptr() + start
+    view.copy_(x)
+    return view
+
+
+def expert_row_starts(E, N, ld_bytes, gs_bytes, byte0=0):
+    return [byte0 + e * gs_bytes + n * ld_bytes for e in range(E) for n in range(N)]
+
+
+def rows_distinct_at(x, starts, others=()):
+    """:func:`rows_distinct` for rows at the byte offsets ``starts`` (from the guard's end):
+    pairwise distinct rows, and the bytes 2^31 and 2^32 before and behind a row's start are the
+    start of another row or padding, never the inside of a row of ``x`` or of ``others`` (pairs
+    ``(starts, row_bytes)`` of further views in the same backing)."""
+    import bisect
+
+    R, C = x.shape
+    assert len(starts) == R
+    assert int(torch.unique(x.to(torch.float32), dim=0).shape[0]) == R, "two rows are equal"
+    for st, nbytes in ((starts, C * x.element_size()),) + tuple(others):
+        order = sorted(st)
+        for s0 in starts:
+            for d in (-2 ** 32, -2 ** 31, 2 ** 31, 2 ** 32):
+                o = s0 + d
+                i = bisect.bisect_right(order, o) - 1
+                assert i < 0 or o == order[i] or o >= order[i] + nbytes, (s0, d)

@@ -510,3 +510,172 @@ def test_nan_padded_fills_with_the_nonfinite_poison():
     assert int((whole(s) == 255).sum()) == 8 * s.stride(0) - 80
     q = X.nan_padded(torch.zeros((5, 16), dtype=torch.uint8), "fp4")
     assert int((whole(q) == 0x77).sum()) == 8 * q.stride(0) - 80
+
+
+# ---------------------------------------------------------------------------- code points, A16 range
+def _decode_e2m1(code):
+    s, e, m = code >> 3, (code >> 1) & 3, code & 1
+    v = m * 0.5 if e == 0 else (1 + m / 2.0) * 2.0 ** (e - 1)
+    return -v if s else v
+
+
+def test_decode_tables_against_bit_field_decoders():
+    import math
+
+    e2 = X.e2m1_values()
+    assert e2.tolist() == [_decode_e2m1(c) for c in range(16)]
+    assert bool(torch.signbit(e2[8])) and float(e2[8]) == 0.0 and float(e2[15]) == -6.0
+    e4 = X.e4m3_values()
+    model = [_decode_e4m3(c) for c in range(256)]
+    for c in range(256):
+        assert (math.isnan(model[c]) and math.isnan(float(e4[c]))) or float(e4[c]) == model[c], c
+    assert bool(torch.signbit(e4[0x80]))
+    # the library's own table and packing agree with the tests'
+    from ddlb_amd.ops import mx
+
+    nib = torch.arange(32).reshape(1, 32) % 16
+    assert torch.equal(mx.pack_e2m1(nib).view(torch.uint8), X.pack_nibbles(nib))
+    assert torch.equal(mx.unpack_e2m1(X.pack_nibbles(nib)).double(), e2[nib])
+    x = ints((4, 64), torch.float32, _gen(51))
+    assert torch.equal(X.decode64(X.ints_as_e2m1(x), torch.full((4, 2), 127), "e2m1"), x.double())
+
+
+@pytest.mark.parametrize("fmt", ["e4m3", "e2m1"])
+def test_code_cases_can_fail(fmt):
+    """The construction of ``tests/test_gemm_codes_gpu.py``: every code on the diagonal of the
+    reference under its own row's byte, and CPU models of two faults change it: the two nibbles
+    of a byte swapped (every E2M1 row), the scale byte taken from the neighbouring block (every
+    row whose code is not a zero)."""
+    data, s, pos, neg0 = X.code_case(fmt)
+    R, K = data.shape[0], X.CODE_K
+    table = X.e4m3_values() if fmt == "e4m3" else X.e2m1_values()
+    codes = [c for c in range(256) if c not in (0x7F, 0xFF)] if fmt == "e4m3" else \
+        [r // 2 for r in range(32)]
+    assert R == len(codes) == (254 if fmt == "e4m3" else 32)
+    p = X.one_hot(pos, K)
+    ref = X.decode64(data, s, fmt) @ p.t()
+    blk = pos // 32
+    own = s[torch.arange(R), blk].long()
+    assert set(own.tolist()) == {125, 126, 127, 128, 129}
+    assert bool((pos % 32 == torch.arange(R) % 32).all()) and bool((blk[1:] != blk[:-1]).all())
+    want = table[torch.tensor(codes)] * pow2_f64(own - 127)
+    assert torch.equal(ref.diagonal(), want + 0.0)
+    assert int(neg0.sum()) == (1 if fmt == "e4m3" else 2)
+    live = want != 0
+    assert int((~live).sum()) == (2 if fmt == "e4m3" else 4)
+    # every lane of the expansion and every pack slot meets a code that is no integer
+    ints7 = {-3.0, -2.0, -1.0, 0.0, 1.0, 2.0, 3.0}
+    assert sum(float(table[c]) not in ints7 for c in codes) >= (8 if fmt == "e2m1" else 200)
+    for shift in (1, -1):                                            # the neighbouring block's byte
+        got = X.decode64(data, torch.roll(s, shift, dims=1), fmt) @ p.t()
+        assert bool((got.diagonal() != ref.diagonal())[live].all())
+    if fmt == "e2m1":
+        swapped = (data << 4) | (data >> 4)
+        got = X.decode64(swapped, s, fmt) @ p.t()
+        assert bool((got.diagonal() != ref.diagonal()).all())
+        assert bool((ref.diagonal() == 0)[~live].all()) and bool((got.diagonal() != 0)[~live].all())
+        nib = X.unpack_nibbles(data)
+        other = nib[torch.arange(R), pos ^ 1]
+        assert bool((other % 8 != 0).all()) and bool((other != torch.tensor(codes)).all())
+        assert bool((pos % 2 == torch.arange(R) % 2).all())          # low and high nibble
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("fmt", ["mx", "mxfp4"])
+def test_a16_range_predicate_against_brute_force(fmt, dt):
+    """All pairs, one by one: the value (``math.ldexp``) survives the round trip through ``dt``
+    and is no subnormal of it. The counts are the ones the GPU test reports."""
+    import math
+
+    dec = _decode_e4m3 if fmt == "mx" else _decode_e2m1
+    ncodes = 256 if fmt == "mx" else 16
+    pairs = [(c, sb) for c in range(ncodes) if not math.isnan(dec(c)) for sb in range(1, 255)]
+    v = torch.tensor([math.ldexp(dec(c), sb - 127) for c, sb in pairs], dtype=torch.float64)
+    back = v.to(dt).double()
+    ok = (back == v) & ((v == 0) | (v.abs() >= torch.finfo(dt).tiny))
+    mask = X.a16_range_mask(fmt, dt)
+    assert int(ok.sum()) == int(mask.sum())
+    brute = torch.zeros_like(mask)
+    idx = torch.tensor(pairs)[ok]
+    brute[idx[:, 0], idx[:, 1]] = True
+    assert torch.equal(brute, mask)
+    assert int(mask.sum()) == {("mx", torch.bfloat16): 63514, ("mx", torch.float16): 8068,
+                               ("mxfp4", torch.bfloat16): 4050,
+                               ("mxfp4", torch.float16): 928}[(fmt, dt)]
+    # the launch layout holds every pair once, at the place the one-hot ``a`` reads
+    data, s, want, used = X.a16_range_case(fmt, mask.nonzero())
+    assert int(used.sum()) == int(mask.sum()) and data.shape[0] == -(-int(mask.sum()) // 64)
+    deq = X.decode64(data, s, "e4m3" if fmt == "mx" else "e2m1")
+    a = torch.zeros((64, 2048), dtype=torch.float64)
+    for m in range(64):
+        a[m, 32 * m:32 * m + 32] = 1.0
+    assert torch.equal(a @ deq.t(), want + 0.0)
+    assert torch.equal(want.to(torch.float32).double(), want)
+
+
+def test_family_far_operand_rows_are_distinct_at_the_pitches_used():
+    """Every far operand of the skinny / A16 / W4A8 far tests, CPU-drawn as the GPU tests draw
+    them, on the pitch its case uses; the scale tensors on both sides of their gates; the
+    experts' strided views."""
+    assert 25 * X.SKINNY_PITCH < 2 ** 31 < 26 * X.SKINNY_PITCH
+    assert 51 * X.SKINNY_PITCH < 2 ** 32 < 52 * X.SKINNY_PITCH
+    assert X.FAR_EXPERT > 2 ** 31 and X.FAR_EXPERT % 16 == 0 and X.FAR_EXPERT_SCALES % 16 == 0
+    for fam in X.FAMILIES:
+        tiled = fam == "w4a8"
+        K = 256 if tiled else X.FAR_K
+        for dt in (torch.bfloat16, torch.float16) if fam.startswith("a16") else (torch.bfloat16,):
+            (M, N), pitch = (X.FAR_TILED, X.FAR_PITCH) if tiled else (X.SKINNY_AC, X.SKINNY_PITCH)
+            X.rows_distinct(X.family_case(fam, M, N, K, dt)[0], pitch)
+            M, N = X.FAR_TILED[::-1] if tiled else X.SKINNY_W
+            X.rows_distinct(X.family_case(fam, M, N, K, dt)[1], X.FAR_PITCH)
+        # the scale gates
+        M, N = (130, 140) if tiled else (17, 152)
+        a, w, s_a, s_w, _ = X.family_case(fam, M, N, K)
+        for sc, rows, form in ((s_a, M, X.FAMILIES[fam][0]), (s_w, N, X.FAMILIES[fam][1])):
+            if sc is None:
+                continue
+            al = 4 if tiled else {"fp8": 4, "fp4": 8}[form]
+            pred = X.a16_scale_rows_ok if fam.startswith("a16") else X.scale_rows_ok
+            last, nxt = X.gate_ld(lambda ld: pred(rows, ld), al)
+            assert nxt == last + al and rows * last < 2 ** 31 <= rows * nxt
+            X.rows_distinct(sc, last)
+            X.rows_distinct(sc, nxt)
+        # the grouped forms: w and w_scale FAR_EXPERT apart, a on its pitch
+        T, N, E = (140, 130, 3) if tiled else (26, 152, 3)
+        a, w, s_a, s_w, _ = X.family_case(fam, T, E * N, K)
+        ldw, lds = w.shape[1] * w.element_size() + 16, K // 32 + 8
+        starts = X.expert_row_starts(E, N, ldw, X.FAR_EXPERT)
+        s_starts = X.expert_row_starts(E, N, lds, X.FAR_EXPERT, X.FAR_EXPERT_SCALES)
+        assert N * ldw <= X.FAR_EXPERT_SCALES and X.FAR_EXPERT_SCALES + N * lds < 2 ** 20
+        X.rows_distinct_at(w, starts, others=((s_starts, K // 32),))
+        if s_w is not None:
+            X.rows_distinct_at(s_w, s_starts, others=((starts, ldw - 16),))
+        pitch = X.GROUP_A_PITCH["w4a8" if tiled else "skinny"]
+        assert (T - 1) * pitch > 2 ** 32
+        X.rows_distinct(a, pitch)
+    # rows_distinct_at sees what rows_distinct sees
+    x = X.far_operands(9, 7, 64, torch.bfloat16)[0]
+    X.rows_distinct_at(x, [r * SMALL_LD for r in range(9)])
+    with pytest.raises(AssertionError):
+        X.rows_distinct_at(x, [r * ((2 ** 31 - 32) // 4) for r in range(9)])
+    assert X.a16_scale_rows_ok(152, 8) and not X.a16_scale_rows_ok(152, 2 ** 31 // 152 + 8)
+    assert X.a16_scale_rows_ok(2, 2 ** 29, 1) and not X.a16_scale_rows_ok(2, 2 ** 29, 2)
+
+
+def test_far_experts_places_experts_and_rows():
+    E, N, C = 3, 4, 24
+    x = ints((E * N, C), torch.float32, _gen(52)).to(FP8).reshape(E, N, C)
+    backing = X.far_backing(2 * 8192 + 2048, guard=SMALL_GUARD, device="cpu")
+    v = X.far_experts(backing, x, 64, 8192, byte0=32)
+    assert tuple(v.shape) == (E, N, C) and v.stride() == (8192, 64, 1)
+    assert v.data_ptr() == backing.data_ptr() + SMALL_GUARD + 32
+    assert torch.equal(v.view(torch.uint8), x.view(torch.uint8))
+    s = torch.arange(E * N * 2, dtype=torch.uint8).reshape(E, N, 2)
+    v2 = X.far_experts(backing, s, 8, 8192, byte0=1024, fill=None)
+    assert torch.equal(v2, s) and torch.equal(v.view(torch.uint8), x.view(torch.uint8))
+    rest = backing.clone()
+    torch.as_strided(rest, (E, N, C), (8192, 64, 1), SMALL_GUARD + 32).fill_(0x4A)
+    torch.as_strided(rest, (E, N, 2), (8192, 8, 1), SMALL_GUARD + 1024).fill_(0x4A)
+    assert bool((rest == 0x4A).all())                                # POISON 5.0 as e4m3
+    with pytest.raises(AssertionError):
+        X.far_experts(backing, x, 64, 8192, byte0=2048)              # past the backing's end

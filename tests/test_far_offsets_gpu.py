@@ -21,6 +21,14 @@ dimensions on both sides from their Python copies, and both sides must be exact:
   4. ``scale_operands_ok()`` / the ``c_scale_ld`` check: ``rows * scale_ld < 2^31``, a refusal
      (of ``gemm()`` and of the native entry) from there on.
 
+Section e runs the kernel families that came later, each with its own entry and addressing code:
+``gemm_skinny`` (MX-fp8, MXFP4, W4A8), ``gemm_skinny_a16`` (MXFP4, MX-fp8, 16-bit weights) and the
+tiled ``gemm_w4a8`` (both tiles), dense with ``a``, ``w`` or ``c`` far, with a gated quantised
+output far, grouped with the experts' ``w`` / ``w_scale`` 2^31 + 2^20 bytes apart, and every scale
+tensor on both sides of its ``rows * stride < 2^31`` gate. Out of scope there: the skinny K-split
+workspace past 2^31 bytes (contiguous, so ``S * M * N > 2^29`` floats: no reference of a few
+seconds; its index arithmetic is ``int64_t`` as read).
+
 Out of scope: the in-kernel all-gather's 1 GiB copy-unit gate (``gemm_launch``'s
 ``flag_rows * lda * esz / ag_parts`` check). At world 1 there is no copy unit to run.
 
@@ -622,6 +630,345 @@ def test_transposing_quantiser_native_past_4gib(far, fmt, dtype, which):
             untouched_far(backing, view)
         else:
             _near_untouched(buf, C, cols)
+
+
+# ---------------------------------------------------------------------------- e. skinny, A16, W4A8
+# The three families of tests/_exact.py FAMILIES: gemm_skinny (three operand forms),
+# gemm_skinny_a16 (three weight forms) and the tiled gemm_w4a8 (two tiles). Integer operands
+# under scale bytes 125..129, CPU-drawn (family_case), the fp64 product as the reference.
+FP4 = torch.float4_e2m1fn_x2
+F16 = torch.float16
+SKINNY_FAMS = [f for f in X.FAMILIES if f.startswith("skinny")]
+A16_FAMS = [f for f in X.FAMILIES if f.startswith("a16")]
+W4A8_TILES = ("256x128", "128x128")
+ALL_FAMS = [(f, None) for f in SKINNY_FAMS + A16_FAMS] + [("w4a8", t) for t in W4A8_TILES]
+FAM_IDS = [f if t is None else f"{f}-{t}" for f, t in ALL_FAMS]
+SCALE_ALIGN = {"fp8": 4, "fp4": 8}   # a scale tensor's alignment by its operand's form ...
+W4A8_ALIGN = 4                       # ... but the tiled W4A8 kernel reads one word per K-tile
+
+
+def _typed(x, fmt):
+    """A CPU or device tensor of ``family_case`` as the kernels take it."""
+    x = x.to(DEV)
+    return x.view(FP4) if fmt == "fp4" else x
+
+
+def _near(x, fmt):
+    return _typed(padded(x.to(DEV)), fmt)
+
+
+def _call(fam, A, W, out, s_a, s_w, **kw):
+    from ddlb_amd.ops import gemm as G
+
+    if fam.startswith("skinny"):
+        return G.gemm_skinny(A, W, out, a_scale=s_a, w_scale=s_w, **kw)
+    if fam.startswith("a16"):
+        return G.gemm_skinny_a16(A, W, out, w_scale=s_w, **kw)
+    return G.gemm_w4a8(A, W, out, a_scale=s_a, w_scale=s_w, **kw)
+
+
+def _call_grouped(fam, A, W, offs, out, s_a, s_w, **kw):
+    from ddlb_amd.ops import gemm as G
+
+    if fam.startswith("skinny"):
+        return G.gemm_skinny_grouped(A, W, offs, out, a_scale=s_a, w_scale=s_w, **kw)
+    if fam.startswith("a16"):
+        return G.gemm_skinny_a16_grouped(A, W, offs, out, w_scale=s_w, **kw)
+    return G.gemm_w4a8_grouped(A, W, offs, out, a_scale=s_a, w_scale=s_w, **kw)
+
+
+def _dev(t):
+    return None if t is None else t.to(DEV)
+
+
+def _family_far(far, fam, which, M, N, pitch, dt=BF16, K=X.FAR_K, **kw):
+    """One dense call of ``fam`` with ``which`` ("a", "w" or "c") far on ``pitch``, f32 output."""
+    fa, fw = X.FAMILIES[fam]
+    a, w, s_a, s_w, ref = X.family_case(fam, M, N, K, dt)
+    backing = far.get()
+    if which == "a":
+        X.rows_distinct(a, pitch)
+        A, W = _typed(far_view(backing, a.to(DEV), pitch), fa), _near(w, fw)
+    elif which == "w":
+        X.rows_distinct(w, pitch)
+        A, W = _near(a, fa), _typed(far_view(backing, w.to(DEV), pitch), fw)
+    else:
+        A, W = _near(a, fa), _near(w, fw)
+    if which == "c":
+        C = far_out(backing, M, N, F32, pitch)
+    else:
+        buf, C = sentinel_out(M, N, F32)
+    assert _call(fam, A, W, C, _dev(s_a), _dev(s_w), **kw) is C
+    torch.cuda.synchronize()
+    want = ref.to(F32).to(DEV)
+    bad = (C != want).nonzero()
+    assert bad.numel() == 0, (f"{fam} {kw} {(M, N, K)} {which} far at pitch {pitch}: "
+                              f"{bad.shape[0]} wrong elements, the first at {bad[0].tolist()}")
+    if which == "c":
+        untouched_far(backing, C)
+    else:
+        untouched(buf, M, N)
+
+
+@pytest.mark.parametrize("which", ["a", "w", "c"])
+@pytest.mark.parametrize("ks", [1, 2])
+@pytest.mark.parametrize("fam", SKINNY_FAMS)
+def test_skinny_far(far, fam, ks, which):
+    """``gemm_skinny_kernel``'s A panel, ``wp`` and ``crow`` (``ks = 2``: the partial kernel and
+    ``skinny_reduce_kernel``'s store): 64 rows 80 MiB + 16 apart pass 2^31 at row 26 and 2^32 at
+    row 52; 300 weight rows ``FAR_PITCH`` apart pass them at rows 128 and 256."""
+    assert 25 * X.SKINNY_PITCH < 2 ** 31 < 26 * X.SKINNY_PITCH
+    assert 51 * X.SKINNY_PITCH < 2 ** 32 < 52 * X.SKINNY_PITCH
+    (M, N), pitch = (X.SKINNY_W, FAR_PITCH) if which == "w" else (X.SKINNY_AC, X.SKINNY_PITCH)
+    _family_far(far, fam, which, M, N, pitch, ksplit=ks)
+
+
+@pytest.mark.parametrize("which", ["a", "w", "c"])
+@pytest.mark.parametrize("ks", [1, 2])
+@pytest.mark.parametrize("fam", A16_FAMS)
+def test_skinny_a16_far(far, fam, ks, which):
+    """``gemm_skinny_a16_kernel``, bf16 activations, the shapes of ``test_skinny_far``."""
+    (M, N), pitch = (X.SKINNY_W, FAR_PITCH) if which == "w" else (X.SKINNY_AC, X.SKINNY_PITCH)
+    _family_far(far, fam, which, M, N, pitch, ksplit=ks)
+
+
+@pytest.mark.parametrize("fam", A16_FAMS)
+def test_skinny_a16_f16_weights_far(far, fam):
+    M, N = X.SKINNY_W
+    _family_far(far, fam, "w", M, N, FAR_PITCH, dt=F16, ksplit=2)
+
+
+@pytest.mark.parametrize("which", ["a", "w", "c"])
+@pytest.mark.parametrize("tile", W4A8_TILES)
+def test_w4a8_far(far, tile, which):
+    """``aptr`` / ``wptr`` / ``crow`` of ``gemm_w4a8_kernel``: ragged 300 x 202 on ``FAR_PITCH``
+    (W far: 202 x 300), the clamped row loads of the last tiles included."""
+    M, N = X.FAR_TILED if which != "w" else X.FAR_TILED[::-1]
+    _family_far(far, "w4a8", which, M, N, FAR_PITCH, K=256, tile=tile)
+
+
+def _chain(ref64, glu, fmt):
+    """The specification of a quantised (gated) output: the exact f32 product, ``glu_reference``,
+    the row quantiser's reference; ``(data bytes, scale bytes)``."""
+    from ddlb_amd.ops import gemm as G
+    from ddlb_amd.ops import mx
+
+    c = ref64.to(F32).to(DEV)
+    h = G.glu_reference(c, "none") if glu else c
+    q, s = (mx.quantize_mxfp4_reference if fmt == "mxfp4" else mx.quantize_mx_reference)(h)
+    return q.view(torch.uint8), s
+
+
+def _quant_far(far, fam, M, N, K, pitch, glu, fmt, **kw):
+    """``out`` far on ``pitch``, ``out_scale`` near: data and scales byte for byte."""
+    from ddlb_amd.ops import gemm as G
+
+    fa, fw = X.FAMILIES[fam]
+    a, w, s_a, s_w, ref = X.family_case(fam, M, N, K)
+    q_ref, s_ref = _chain(ref, glu, fmt)
+    cols = N // 2 if glu else N
+    assert tuple(s_ref.shape) == (M, cols // 32)
+    backing = far.get()
+    q = far_out(backing, M, q_ref.shape[1], torch.uint8, pitch)
+    sbuf, s = _near_bytes(M, cols // 32, 8)
+    fn = G.gemm_skinny if fam.startswith("skinny") else G.gemm_w4a8
+    fn(_near(a, fa), _near(w, fw), q.view(G.out_quant_dtype(fmt)), a_scale=_dev(s_a),
+       w_scale=_dev(s_w), glu=glu, out_quant=fmt, out_scale=s, **kw)
+    torch.cuda.synchronize()
+    assert torch.equal(s, s_ref), f"{int((s != s_ref).sum())} scale bytes differ"
+    assert torch.equal(q, q_ref), f"{int((q != q_ref).sum())} data bytes differ"
+    untouched_far(backing, q)
+    _near_untouched(sbuf, M, cols // 32)
+
+
+@pytest.mark.parametrize("ks", [1, 2])
+@pytest.mark.parametrize("fmt", ["mx", "mxfp4"])
+@pytest.mark.parametrize("fam", SKINNY_FAMS)
+def test_skinny_gated_quantised_out_far(far, fam, fmt, ks):
+    """``skinny_store4``'s quantised tail behind the unsplit kernel and behind
+    ``skinny_epilogue_kernel``: 64 rows of 256 gated columns on the 80 MiB pitch."""
+    _quant_far(far, fam, 64, 512, X.FAR_K, X.SKINNY_PITCH, True, fmt, ksplit=ks)
+
+
+@pytest.mark.parametrize("glu", [False, True], ids=["plain", "glu"])
+@pytest.mark.parametrize("tile", W4A8_TILES)
+def test_w4a8_quantised_out_far(far, tile, glu):
+    """The MX-fp8 epilogue's ``crow``: 300 rows ``FAR_PITCH`` apart."""
+    _quant_far(far, "w4a8", 300, 256, 256, FAR_PITCH, glu, "mx", tile=tile)
+
+
+# The 32-bit scale gates of the three families, each at its edge.
+def _no_load():
+    raise AssertionError("load() was reached")
+
+
+def _scale_align(fam, which):
+    if fam == "w4a8":
+        return W4A8_ALIGN
+    return SCALE_ALIGN[X.FAMILIES[fam][0 if which == "a_scale" else 1]]
+
+
+GATED_SCALES = [(f, t, w) for f, t in ALL_FAMS for w in ("a_scale", "w_scale")
+                if X.FAMILIES[f][0 if w == "a_scale" else 1] in SCALE_ALIGN]
+
+
+@pytest.mark.parametrize("fam,tile,which", GATED_SCALES,
+                         ids=[f"{f}{'' if t is None else '-' + t}-{w}" for f, t, w in GATED_SCALES])
+def test_family_operand_scale_gates(far, monkeypatch, fam, tile, which):
+    """``a_scale`` / ``w_scale`` on the largest aligned row stride the Python gate takes
+    (``rows * stride < 2^31``; A16: ``max(E, 1) * N * stride``): exact, nothing outside C written.
+    On the next stride Python refuses before ``load()``, and so does the native entry of the
+    tiled W4A8 GEMM (the only one of the three whose kernel keeps these offsets in 32 bits)."""
+    from ddlb_amd.ops import gemm as G
+
+    M, N, K = (130, 140, 256) if fam == "w4a8" else (17, 152, X.FAR_K)
+    fa, fw = X.FAMILIES[fam]
+    a, w, s_a, s_w, ref = X.family_case(fam, M, N, K)
+    rows = M if which == "a_scale" else N
+    pred = (lambda ld: X.a16_scale_rows_ok(rows, ld)) if fam.startswith("a16") else \
+        (lambda ld: X.scale_rows_ok(rows, ld))
+    last, nxt = gate_ld(pred, _scale_align(fam, which))
+    assert rows * last < 2 ** 31 <= rows * nxt
+    backing = far.get()
+    A, W, want = _near(a, fa), _near(w, fw), ref.to(F32).to(DEV)
+    kw = dict(tile=tile) if fam == "w4a8" else dict(ksplit=2)
+    for ld in (last, nxt):
+        src = s_a if which == "a_scale" else s_w
+        X.rows_distinct(src, ld)
+        sc = far_view(backing, src.to(DEV), ld)
+        sa, sw = (sc, _dev(s_w)) if which == "a_scale" else (_dev(s_a), sc)
+        buf, C = sentinel_out(M, N, F32)
+        if ld == last:
+            _call(fam, A, W, C, sa, sw, **kw)
+            torch.cuda.synchronize()
+            assert torch.equal(C, want)
+            untouched(buf, M, N)
+            continue
+        assert far_span(rows, K // 32, ld) + FAR_GUARD <= backing.numel()
+        with monkeypatch.context() as mp:
+            mp.setattr(G, "load", _no_load)
+            with pytest.raises(ValueError, match="spans 2 GiB"):
+                _call(fam, A, W, C, sa, sw, **kw)
+        if fam == "w4a8":
+            with pytest.raises(RuntimeError, match="invalid"):
+                G._run_w4a8((M, N, K, 0, F32), A, W, None, C, sa, sw, tile, "none", False, None,
+                            None, None)
+        torch.cuda.synchronize()
+        untouched(buf, 0, 0)
+
+
+@pytest.mark.parametrize("fam,tile", [(f, None) for f in SKINNY_FAMS] +
+                         [("w4a8", t) for t in W4A8_TILES],
+                         ids=SKINNY_FAMS + [f"w4a8-{t}" for t in W4A8_TILES])
+def test_family_output_scale_gates(far, monkeypatch, fam, tile):
+    """``out_scale`` of ``gemm_skinny`` / ``gemm_w4a8`` (``out_quant="mx"``) on the largest stride
+    with ``M * stride < 2^31``: the reference quantiser's bytes and nothing else in the backing;
+    the next stride is refused before ``load()`` (W4A8: by the native entry too)."""
+    from ddlb_amd.ops import gemm as G
+
+    M, N, K = (130, 128, 256) if fam == "w4a8" else (17, 128, X.FAR_K)
+    fa, fw = X.FAMILIES[fam]
+    a, w, s_a, s_w, ref = X.family_case(fam, M, N, K)
+    q_ref, s_ref = _chain(ref, False, "mx")
+    last, nxt = gate_ld(lambda ld: X.scale_rows_ok(M, ld), 4)
+    backing = far.get()
+    A, W, sa, sw = _near(a, fa), _near(w, fw), _dev(s_a), _dev(s_w)
+    fn = G.gemm_skinny if fam.startswith("skinny") else G.gemm_w4a8
+    kw = dict(tile=tile) if fam == "w4a8" else dict(ksplit=2)
+    for ld in (last, nxt):
+        out_scale = far_out(backing, M, N // 32, torch.uint8, ld)
+        qbuf, q = _near_bytes(M, N, 32)
+        if ld == last:
+            fn(A, W, q.view(FP8), a_scale=sa, w_scale=sw, out_quant="mx", out_scale=out_scale,
+               **kw)
+            torch.cuda.synchronize()
+            assert torch.equal(out_scale, s_ref) and torch.equal(q, q_ref)
+            untouched_far(backing, out_scale)
+            _near_untouched(qbuf, M, N)
+            continue
+        assert far_span(M, N // 32, ld) + FAR_GUARD <= backing.numel()
+        with monkeypatch.context() as mp:
+            mp.setattr(G, "load", _no_load)
+            with pytest.raises(ValueError, match="spans 2 GiB"):
+                fn(A, W, q.view(FP8), a_scale=sa, w_scale=sw, out_quant="mx",
+                   out_scale=out_scale, **kw)
+        if fam == "w4a8":
+            with pytest.raises(RuntimeError, match="invalid"):
+                G._run_w4a8((M, N, K, 0, FP8), A, W, None, q.view(FP8), sa, sw, tile, "none",
+                            False, "mx", out_scale, None)
+        torch.cuda.synchronize()
+        untouched_far(backing, out_scale[:0])
+        _near_untouched(qbuf, 0, 0)
+
+
+# The grouped forms: E = 3 with an empty first group, so the experts used are the two far ones.
+def _grouped_shape(fam):
+    """``(T, N, K, offsets)``: sizes (0, 17, 5) from row 2 of 26, or (0, 130, 7) of 140."""
+    if fam == "w4a8":
+        return 140, 130, 256, [2, 2, 132, 139]
+    return 26, 152, X.FAR_K, [2, 2, 19, 24]
+
+
+@pytest.mark.parametrize("which", ["w", "a", "out"])
+@pytest.mark.parametrize("fam,tile", ALL_FAMS, ids=FAM_IDS)
+def test_family_grouped_far(far, fam, tile, which):
+    """The ``g * w_gstride`` / ``g * w_scale_gstride`` expert steps (``w`` and ``w_scale`` strided
+    views of the backing ``FAR_EXPERT`` bytes apart: no Python check bounds that stride), the
+    grouped A rows and the grouped output rows. Every group equals the dense call on its slice
+    and the fp64 product; rows outside the groups keep the sentinel."""
+    fa, fw = X.FAMILIES[fam]
+    E = 3
+    T, N, K, raw = _grouped_shape(fam)
+    a, w, s_a, s_w, ref = X.family_case(fam, T, E * N, K)
+    kw = dict(tile=tile) if fam == "w4a8" else dict(ksplit=2)
+    backing = far.get()
+    w3 = w.reshape(E, N, -1)
+    s3 = None if s_w is None else s_w.reshape(E, N, -1)
+    a_pitch = X.GROUP_A_PITCH["w4a8" if fam == "w4a8" else "skinny"]
+    assert (T - 1) * a_pitch > 2 ** 32
+    if which == "w":
+        ldw = w3.shape[2] * w3.element_size() + 16
+        lds = K // 32 + 8
+        starts = X.expert_row_starts(E, N, ldw, X.FAR_EXPERT)
+        s_starts = X.expert_row_starts(E, N, lds, X.FAR_EXPERT, X.FAR_EXPERT_SCALES)
+        X.rows_distinct_at(w, starts, others=((s_starts, K // 32),) if s3 is not None else ())
+        W = _typed(X.far_experts(backing, w3.to(DEV), ldw, X.FAR_EXPERT), fw)
+        assert W[1].data_ptr() - W[0].data_ptr() > 2 ** 31
+        assert W[2].data_ptr() - W[0].data_ptr() > 2 ** 32
+        if s3 is not None:
+            X.rows_distinct_at(s_w, s_starts, others=((starts, ldw - 16),))
+            S = X.far_experts(backing, s3.to(DEV), lds, X.FAR_EXPERT, X.FAR_EXPERT_SCALES,
+                              fill=None)
+        else:
+            S = None
+    else:
+        W = _typed(torch.stack([padded(w3[e].to(DEV)) for e in range(E)]), fw)
+        S = _dev(s3)
+    if which == "a":
+        X.rows_distinct(a, a_pitch)
+        A = _typed(far_view(backing, a.to(DEV), a_pitch), fa)
+    else:
+        A = _near(a, fa)
+    if which == "out":
+        C = far_out(backing, T, N, F32, a_pitch)
+    else:
+        buf, C = sentinel_out(T, N, F32)
+    offs = torch.tensor(raw, dtype=torch.int32, device=DEV)
+    _call_grouped(fam, A, W, offs, C, _dev(s_a), S, **kw)
+    torch.cuda.synchronize()
+    want = ref.to(F32).to(DEV)
+    for e in range(E):
+        r = slice(raw[e], raw[e + 1])
+        if raw[e + 1] == raw[e]:
+            continue
+        assert torch.equal(C[r], want[r, e * N:(e + 1) * N]), (fam, which, e)
+        one = _call(fam, A[r], W[e], None, None if s_a is None else _dev(s_a)[r],
+                    None if S is None else S[e], out_dtype=F32, **kw)
+        assert torch.equal(C[r], one), (fam, which, e)
+    if which == "out":
+        untouched_far(backing, C, rows=slice(raw[0], raw[-1]))
+    else:
+        untouched(buf, T, N, rows=slice(raw[0], raw[-1]))
 
 
 # ---------------------------------------------------------------------------- d. copy, reduce

@@ -80,6 +80,19 @@ def test_exact_on_integers(wfmt, dt, case):
     assert torch.equal(out, (a.double() @ wd.t()).to(F32).to(out.dtype))
 
 
+@pytest.mark.parametrize("ks", (1, 3))
+@pytest.mark.parametrize("glu", (False, True), ids=("dense", "glu"))
+@dtypes
+@forms
+def test_six_strips(wfmt, dt, glu, ks):
+    """Six workgroups along N: ``N = 5 STRIP + 1`` (the last strip one weight row), and gated at
+    ``N = 6 STRIP`` against ``glu_reference`` of the exact f32 product."""
+    a, w, s, wd = _case(wfmt, dt, 17, 6 * STRIP if glu else 5 * STRIP + 1, 5)
+    want = (a.double() @ wd.t()).to(F32)
+    out = _run(a, w, s, F32, ksplit=ks, glu=glu)
+    assert torch.equal(out, G.glu_reference(want) if glu else want)
+
+
 @pytest.mark.parametrize("ks", (1, 2))
 @pytest.mark.parametrize("raw", ([2, 2, 5, 22, 22, 23], [2, -7, 5, 22, 9, 999]),
                          ids=("sorted", "garbage"))

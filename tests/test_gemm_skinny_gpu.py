@@ -9,8 +9,8 @@ formats can carry: NaN bytes (fp8) and the scale byte 255 (both formats)."""
 import pytest
 import torch
 
-from _exact import (FAR_PITCH, FP8, classes64, dequant64, exact_scaled, extreme_scales, far_backing,
-                    far_span, far_view, ints, nan_padded, same, sentinel_out, untouched)
+from _exact import (FP8, classes64, dequant64, exact_scaled, extreme_scales, ints, nan_padded,
+                    same, sentinel_out, untouched)
 from ddlb_amd.ops import gemm as G
 
 pytestmark = pytest.mark.gpu
@@ -166,12 +166,24 @@ def test_activation_within_one_ulp(act):
         assert bool((err <= 2.0 ** -14 + rtol * want.abs()).all()), float(err.max())
 
 
-def test_far_weight_rows():
-    """W rows ``FAR_PITCH`` apart behind the 2 GiB guard: rows from 128 on lie past 2^31."""
-    a, w, s_a, s_w, a8, w8 = _case("mx", 17, STRIP + 24, 5)
-    backing = far_backing(far_span(w.shape[0], w.shape[1], FAR_PITCH))
-    out = _run(a, far_view(backing, w, FAR_PITCH), s_a, s_w, F32, ksplit=2)
+@pytest.mark.parametrize("ks", (1, 3))
+@pytest.mark.parametrize("fmt", FMTS)
+def test_six_strips(fmt, ks):
+    """``N = 5 STRIP + 1``: six workgroups along N, the last one a single weight row."""
+    a, w, s_a, s_w, a8, w8 = _case(fmt, 17, 5 * STRIP + 1, 5, centre=127)
+    out = _run(a, w, s_a, s_w, F32, ksplit=ks)
     assert torch.equal(out, exact_scaled(a8, w8, s_a, s_w).to(F32))
+
+
+@pytest.mark.parametrize("ks", (1, 3))
+@pytest.mark.parametrize("fmt", FMTS)
+def test_six_strips_gated(fmt, ks):
+    """``N = 6 STRIP`` gated: ``glu_reference`` of the exact f32 product, 3 STRIP columns."""
+    a, w, s_a, s_w, a8, w8 = _case(fmt, 17, 6 * STRIP, 5, centre=127)
+    buf, out = sentinel_out(17, 3 * STRIP, F32)
+    G.gemm_skinny(a, w, out, a_scale=s_a, w_scale=s_w, ksplit=ks, glu=True)
+    assert torch.equal(out, G.glu_reference(exact_scaled(a8, w8, s_a, s_w).to(F32)))
+    untouched(buf, 17, 3 * STRIP)
 
 
 @pytest.mark.parametrize("dispatch,top_k", (("torch", 1), ("native", 2)))

@@ -50,6 +50,23 @@ def test_exact_on_integers(case):
     assert torch.equal(out, exact_scaled(a8, w8, s_a, s_w).to(F32).to(case["out"]))
 
 
+@pytest.mark.parametrize("ks", (1, 3))
+@pytest.mark.parametrize("glu", (False, True), ids=("dense", "glu"))
+def test_six_strips(glu, ks):
+    """Six workgroups along N: ``N = 5 STRIP + 1`` (the last strip one weight row), and gated at
+    ``N = 6 STRIP``."""
+    N = 6 * STRIP if glu else 5 * STRIP + 1
+    a, w, s_a, s_w, a8, w8 = _case(17, N, 3, centre=127)
+    want = exact_scaled(a8, w8, s_a, s_w).to(F32)
+    if not glu:
+        assert torch.equal(_run(a, w, s_a, s_w, F32, ksplit=ks), want)
+        return
+    buf, out = sentinel_out(17, N // 2, F32)
+    G.gemm_skinny(a, w, out, a_scale=s_a, w_scale=s_w, ksplit=ks, glu=True)
+    assert torch.equal(out, G.glu_reference(want))
+    untouched(buf, 17, N // 2)
+
+
 @pytest.mark.parametrize("ks", (1, 2))
 @pytest.mark.parametrize("raw", ([2, 2, 5, 22, 22, 23], [2, -7, 5, 22, 9, 999]),
                          ids=("sorted", "garbage"))

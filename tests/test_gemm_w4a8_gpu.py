@@ -109,6 +109,31 @@ def test_grouped_equals_dense_per_group(fused, raw, tile):
         _holds(bufs, slice(o[0], o[-1]), ref)
 
 
+@pytest.mark.parametrize("tile", G.W4A8_TILES)
+@pytest.mark.parametrize("grouped", (False, True), ids=("dense", "grouped"))
+def test_remapped_grid(grouped, tile):
+    """``M = 513``, ``N = 258``: 15 tiles at 128x128 and 9 at 256x128, more than 8 and no multiple
+    of 8, so ``xcd_remap`` is no identity (``q >= 1``, ``r != 0``). Grouped: E = 3, sizes
+    (200, 57, 256), every group against the fp64 product with its expert's weights."""
+    M, N, E = 513, 258, 3
+    a, w, s_a, s_w, a8, w8 = _case(M, N, 1)
+    if not grouped:
+        want = exact_scaled(a8, w8, s_a, s_w).to(F32)
+        assert torch.equal(_run(a, w, s_a, s_w, F32, tile=tile), want)
+        return
+    ws = [_case(M, N + e, 1) for e in range(E)]
+    wg = torch.stack([G._as_bytes(c[1][:N]) for c in ws]).view(w.dtype)
+    sg = torch.stack([c[3][:N] for c in ws])
+    o = [0, 200, 257, 513]
+    buf, out = sentinel_out(M, N, F32)
+    G.gemm_w4a8_grouped(a, wg, torch.tensor(o, dtype=torch.int32, device=DEV), out, a_scale=s_a,
+                        w_scale=sg, tile=tile)
+    untouched(buf, M, N)
+    for e in range(E):
+        r = slice(o[e], o[e + 1])
+        assert torch.equal(out[r], exact_scaled(a8[r], ws[e][5][:N], s_a[r], sg[e]).to(F32)), e
+
+
 def test_non_finite():
     """A NaN byte in ``a`` reaches exactly its output row, a scale byte 255 in ``w_scale`` exactly
     its output column."""
