@@ -16,6 +16,7 @@
 #include "comm/comm.h"
 #include "gemm/gemm.h"
 #include "gemm/gemm_skinny.h"
+#include "gemm/gemm_a16.h"
 #include "gemm/gemm_w4a8.h"
 #include "gemm/glu_act.h"
 #include "moe/moe.h"
@@ -319,6 +320,27 @@ PYBIND11_MODULE(_C, m) {
         py::arg("a_scale") = 0, py::arg("w_scale") = 0, py::arg("a_scale_ld") = 0,
         py::arg("w_scale_ld") = 0, py::arg("act") = 0, py::arg("glu") = 0, py::arg("c_scale") = 0,
         py::arg("c_scale_ld") = 0, py::arg("offs") = 0, py::arg("ngroups") = 0,
+        py::arg("w_gstride") = 0, py::arg("w_scale_gstride") = 0, py::arg("stream") = 0);
+  // Tiled A16 GEMM (gemm_a16.h): a bf16 / f16 [M, K] (din), w MXFP4 / MX-fp8 under w_scale (dw =
+  // DT_FP4 / DT_FP8; ldw / w_gstride in w's elements), dense output in din or f32; grouped with
+  // offs / ngroups as gemm_grouped takes them. Not routed through gemm_launch.
+  m.def("gemm_a16",
+        [](uintptr_t a, uintptr_t w, uintptr_t c, int64_t lda, int64_t ldw, int64_t ldc, int M,
+           int N, int K, int din, int dout, int dw, int tile, uintptr_t w_scale,
+           int64_t w_scale_ld, int act, int glu, uintptr_t offs, int ngroups, int64_t w_gstride,
+           int64_t w_scale_gstride, uintptr_t stream) {
+          GemmArgs g = make_args(a, w, c, lda, ldw, ldc, M, N, K, 0, 0, 0, 0);
+          set_scales_epilogue(g, 0, w_scale, 0, w_scale_ld, 0, 0, act, glu);
+          g.grp_offs = (const int*)offs;
+          g.ngroups = ngroups;
+          g.b_gstride = w_gstride;
+          g.b_scale_gstride = w_scale_gstride;
+          check(gemm_a16_launch(g, din, dout, dw, tile, (hipStream_t)stream), "gemm_a16");
+        },
+        py::arg("a"), py::arg("w"), py::arg("c"), py::arg("lda"), py::arg("ldw"), py::arg("ldc"),
+        py::arg("M"), py::arg("N"), py::arg("K"), py::arg("din"), py::arg("dout"), py::arg("dw"),
+        py::arg("tile") = 0, py::arg("w_scale") = 0, py::arg("w_scale_ld") = 0,
+        py::arg("act") = 0, py::arg("glu") = 0, py::arg("offs") = 0, py::arg("ngroups") = 0,
         py::arg("w_gstride") = 0, py::arg("w_scale_gstride") = 0, py::arg("stream") = 0);
   // the launch arithmetic of gemm_skinny.h: (strips, the automatic slice count)
   m.def("skinny_plan", [](int N, int nk, int groups, int cus) {

@@ -66,6 +66,7 @@
 // Built with the flags of gemm_skinny.hip (no packed-f32 VALU): the two files share the epilogue
 // tail and the reduce kernels as source, and the gated test compares their arithmetic byte for
 // byte with the f32 path; the K-loop here has no f32 VALU arithmetic either way.
+#include "gemm_a16_ops.h"
 #include "gemm_skinny_tail.h"
 
 namespace ddlb {
@@ -73,28 +74,6 @@ namespace {
 
 constexpr int PK = kSkinnyPanel, NR = kSkinnyNR, SNT = 64 * kSkinnyWaves;
 constexpr int A16_W4 = 0, A16_W8 = 1, A16_W16 = 2;  // the weight forms
-
-// The conversions and the MFMA of one activation dtype. B: the byte (fp4: two elements) or the
-// half (fp8: two elements) of the source dword.
-template <int DT> struct A16Ops;
-template <> struct A16Ops<DT_BF16> {
-  using Mma = MmaBF16;
-  template <int B> static __device__ __forceinline__ int fp4(unsigned v, float sc) {
-    return __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, sc, B));
-  }
-  template <bool HI> static __device__ __forceinline__ int fp8(unsigned v, float sc) {
-    return __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v, sc, HI));
-  }
-};
-template <> struct A16Ops<DT_F16> {
-  using Mma = MmaF16;
-  template <int B> static __device__ __forceinline__ int fp4(unsigned v, float sc) {
-    return __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(v, sc, B));
-  }
-  template <bool HI> static __device__ __forceinline__ int fp8(unsigned v, float sc) {
-    return __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(v, sc, HI));
-  }
-};
 
 // p arrives as the byte view gemm_skinny_a16_launch forms: lda, ldw, w_gstride in bytes, K in
 // elements. PART / OUT / GLU and the W row map: as gemm_skinny_kernel.

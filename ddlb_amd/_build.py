@@ -55,6 +55,8 @@ SOURCES = [  # heaviest translation units first (the parallel build's critical p
     "gemm/gemm_w4a8.hip",
     "gemm/gemm_w4a8_grouped.hip",
     "gemm/gemm_w4a8_q.hip",
+    "gemm/gemm_a16.hip",
+    "gemm/gemm_a16_grouped.hip",
     "gemm/gemm_skinny.hip",
     "gemm/gemm_skinny_a16.hip",
     "gemm/mx_quant.hip",
@@ -82,7 +84,8 @@ HEADERS = ["gemm/gemm.h", "gemm/gemm_kernels.h", "gemm/gemm_entry.h", "gemm/tile
            "gemm/device_info.h", "gemm/mx_cvt.h", "gemm/mx_quant_in.h", "gemm/row_io.h",
            "gemm/glu_act.h", "gemm/gemm_grouped_kernels.h", "gemm/gemm_kgrouped_kernels.h",
            "gemm/gemm_skinny.h", "gemm/gemm_skinny_tail.h", "gemm/gemm_w4a8.h",
-           "gemm/gemm_w4a8_kernels.h", "moe/moe.h", "moe/moe_route_map.h",
+           "gemm/gemm_w4a8_kernels.h", "gemm/gemm_a16.h", "gemm/gemm_a16_ops.h",
+           "gemm/gemm_a16_kernels.h", "moe/moe.h", "moe/moe_route_map.h",
            "runtime/kernels.h", "comm/comm.h", "runtime/plan.h", "runtime/plan_ir.h"]
 
 

@@ -30,11 +30,15 @@ W4A8 kernel, ``ops.gemm.gemm_w4a8``: fc1 with ``act`` / ``glu`` and ``out_quant=
 fc2. ``fused=False`` there is bf16 fc1 and the row quantiser (gated: f32 fc1, ``ops.glu.glu``,
 the row quantiser).
 
-``fmt="w4a16"`` / ``"w8a16"`` (``kernel="skinny"`` only) is weight-only quantisation: MXFP4 /
-MX-fp8 weights, ``X`` and ``H`` stay 16-bit and nothing is quantised per forward. Both layers run
-``ops.gemm.gemm_skinny_a16`` (fc1 with ``act`` / ``glu``, writing ``H`` in ``X``'s dtype).
-``reference_chain`` for them: the dequantised weights, ``H`` rounded to ``X``'s dtype between the
-layers.
+``fmt="w4a16"`` / ``"w8a16"`` (``kernel="skinny"``, or ``"a16"`` below) is weight-only
+quantisation: MXFP4 / MX-fp8 weights, ``X`` and ``H`` stay 16-bit and nothing is quantised per
+forward. Both layers run ``ops.gemm.gemm_skinny_a16`` (fc1 with ``act`` / ``glu``, writing ``H``
+in ``X``'s dtype). ``reference_chain`` for them: the dequantised weights, ``H`` rounded to ``X``'s
+dtype between the layers.
+
+``kernel="a16"`` (``fmt="w4a16"`` / ``"w8a16"`` only, any ``seq``: prefill) runs the same chain on
+the tiled A16 kernel, ``ops.gemm.gemm_a16``: fc1 with ``act`` / ``glu`` and ``H`` in ``X``'s
+dtype, then fc2.
 
 ``reference()`` is the torch chain on the dequantised operands in fp32:
 ``dequantize(quantize_reference(act(Xd @ W1d.T))) @ W2d.T`` (gated: ``glu_reference`` of the
@@ -45,7 +49,7 @@ from __future__ import annotations
 
 FMTS = ("mx", "mxfp4", "w4a8", "w4a16", "w8a16")
 A16 = "a16"  # the activation "format" of the weight-only formats: not quantised
-KERNELS = ("tiled", "skinny", "mixed")
+KERNELS = ("tiled", "skinny", "mixed", "a16")
 SKINNY_ROWS = 64  # the rows one pass over the weights serves (gemm_skinny)
 
 
@@ -77,11 +81,16 @@ def _check_fmt_kernel(fmt: str, kernel: str) -> int:
         if fmt != "w4a8":
             raise ValueError(f"kernel='mixed' is the tiled W4A8 GEMM: it takes fmt='w4a8' only, "
                              f"not fmt={fmt!r}")
+    elif kernel == "a16":
+        if afmt != A16:
+            raise ValueError(f"kernel='a16' is the tiled A16 GEMM: it takes fmt='w4a16' / "
+                             f"'w8a16' only, not fmt={fmt!r}")
     elif afmt != wfmt and kernel != "skinny":
         raise ValueError(f"fmt={fmt!r} needs kernel='skinny': only the skinny GEMMs multiply "
                          "MX-fp8 or 16-bit activations by narrower MX weights, the tiled kernel "
                          "takes one format for both operands (fmt='w4a8' also runs at any seq "
-                         "with kernel='mixed', the tiled W4A8 GEMM)")
+                         "with kernel='mixed', the tiled W4A8 GEMM; fmt='w4a16' / 'w8a16' with "
+                         "kernel='a16', the tiled A16 GEMM)")
     return 256 if wfmt == "mxfp4" else 128
 
 
@@ -145,6 +154,12 @@ class MxMLP:
 
         from ddlb_amd.ops.gemm import gemm
 
+        if self.kernel == "a16":  # weight-only at any seq: the tiled A16 GEMM
+            from ddlb_amd.ops.gemm import gemm_a16
+
+            h = gemm_a16(self.X, self.w1q, w_scale=self.w1s, act=self.act, glu=self.gated,
+                         tile=self.tile)
+            return gemm_a16(h, self.w2q, self.out, w_scale=self.w2s, tile=self.tile)
         if self.afmt == A16:  # weight-only: nothing is quantised per forward
             from ddlb_amd.ops.gemm import gemm_skinny_a16
 

@@ -45,9 +45,12 @@ goes between it and fc2; ``fused=False`` is the chain the fused epilogue replace
 ``kernel="mixed"`` (``fmt="w4a8"`` only, any number of tokens: prefill) runs both layers on the
 tiled W4A8 kernel, ``ops.gemm.gemm_w4a8_grouped``, with either dispatch; ``fused`` as above.
 
-``fmt="w4a16"`` / ``"w8a16"`` (``kernel="skinny"`` only): weight-only quantisation. The routed
-rows stay bf16 (``ops.moe.gather``, or ``index_select`` with the torch dispatch) and both layers
-run ``ops.gemm.gemm_skinny_a16_grouped``, fc1 gated and writing bf16.
+``fmt="w4a16"`` / ``"w8a16"`` (``kernel="skinny"``, or ``"a16"`` below): weight-only
+quantisation. The routed rows stay bf16 (``ops.moe.gather``, or ``index_select`` with the torch
+dispatch) and both layers run ``ops.gemm.gemm_skinny_a16_grouped``, fc1 gated and writing bf16.
+
+``kernel="a16"`` (``fmt="w4a16"`` / ``"w8a16"`` only, any number of tokens: prefill) runs both
+layers on the tiled A16 kernel, ``ops.gemm.gemm_a16_grouped``, after the same gather.
 """
 
 from __future__ import annotations
@@ -97,7 +100,7 @@ def expert_ids_topk(seq: int, experts: int, k: int, seed: int = 0):
 
 
 DISPATCHES = ("torch", "native")
-KERNELS = ("tiled", "skinny", "mixed")
+KERNELS = ("tiled", "skinny", "mixed", "a16")
 
 
 class MxMoE:
@@ -248,7 +251,7 @@ class MxMoE:
 
     def _forward_a16(self):
         """The weight-only formats: the routed rows stay bf16, nothing is quantised."""
-        from ddlb_amd.ops.gemm import gemm_skinny_a16_grouped
+        from ddlb_amd.ops.gemm import gemm_a16_grouped, gemm_skinny_a16_grouped
 
         if self.dispatch == "native":
             from ddlb_amd.ops.moe import combine, gather, route
@@ -258,9 +261,14 @@ class MxMoE:
         else:
             perm, offsets = self.route()
             xp = self.X.index_select(0, perm)
-        h = gemm_skinny_a16_grouped(xp, self.w1q, offsets, w_scale=self.w1s, act=self.act,
-                                    glu=True)
-        gemm_skinny_a16_grouped(h, self.w2q, offsets, self.ysorted, w_scale=self.w2s)
+        if self.kernel == "a16":
+            h = gemm_a16_grouped(xp, self.w1q, offsets, w_scale=self.w1s, act=self.act, glu=True,
+                                 tile=self.tile)
+            gemm_a16_grouped(h, self.w2q, offsets, self.ysorted, w_scale=self.w2s, tile=self.tile)
+        else:
+            h = gemm_skinny_a16_grouped(xp, self.w1q, offsets, w_scale=self.w1s, act=self.act,
+                                        glu=True)
+            gemm_skinny_a16_grouped(h, self.w2q, offsets, self.ysorted, w_scale=self.w2s)
         if self.dispatch == "native":
             combine(self.ysorted, slot_row, self.gates, out=self.out)
         else:

@@ -1279,6 +1279,55 @@ def gemm_skinny_grouped(a, w, offsets, out=None, *, a_scale, w_scale, out_dtype=
 _A16_FORMS = {"mxfp4": (256, 8), "mx": (128, 4), "same": (64, 0)}
 
 
+def _check_group_layout(what, a, w, offsets, E, N):
+    """What the grouped forms of the skinny A16, W4A8 and A16 GEMMs ask of ``offsets`` and of the
+    experts' weights ``w [E, N, K]`` (the offsets' content is never read)."""
+    if not 1 <= E <= MAX_GROUPS:
+        raise ValueError(f"{what} takes 1 .. {MAX_GROUPS} groups, not {E}")
+    _check_offsets_dtype(offsets)
+    if offsets.dim() != 1 or offsets.shape[0] != E + 1 or not offsets.is_contiguous():
+        raise ValueError(f"offsets must be contiguous with shape ({E + 1},) for {E} groups, "
+                         f"not {tuple(offsets.shape)}")
+    if offsets.device != a.device:
+        raise ValueError(f"offsets is on {offsets.device}, the operands on {a.device}")
+    if E > 1 and w.stride(0) < N * w.stride(1):
+        raise ValueError(f"w needs experts at least N rows apart (strides "
+                         f"{tuple(w.stride())})")
+    if w.stride(0) * w.element_size() % 16:
+        raise ValueError("the experts' weights must be a multiple of 16 bytes apart")
+
+
+def _check_operand_rows(what, a, w):
+    """Unit inner stride and 16-byte-aligned rows of at least K elements, for both operands."""
+    for name, t in (("a", a), ("w", w)):
+        if t.stride(-1) != 1 or t.stride(-2) < t.shape[-1]:
+            raise ValueError(f"{name} needs unit inner stride and rows of at least K (strides "
+                             f"{tuple(t.stride())})")
+        if t.data_ptr() % 16 or t.stride(-2) * t.element_size() % 16:
+            raise ValueError(f"{what} needs 16-byte-aligned rows of {name}")
+
+
+def _check_a16_w_scale(a, w_scale, E, N, K, sal, grouped):
+    """The E8M0 scales of an A16 GEMM's MX weights: uint8 ``[N, K / 32]`` (grouped
+    ``[E, N, K / 32]``), base and strides multiples of ``sal`` bytes, under 2 GiB."""
+    import torch
+
+    shape = ((E,) if grouped else ()) + (N, K // 32)
+    if not isinstance(w_scale, torch.Tensor) or w_scale.dtype != torch.uint8:
+        raise TypeError("w_scale must be a uint8 tensor of E8M0 bytes")
+    if w_scale.device != a.device:
+        raise ValueError(f"w_scale is on {w_scale.device}, the operands on {a.device}")
+    if tuple(w_scale.shape) != shape:
+        raise ValueError(f"w_scale must have shape {shape}, not {tuple(w_scale.shape)}")
+    st = w_scale.stride()
+    if st[-1] != 1 or st[-2] % sal or st[-2] < K // 32 or w_scale.data_ptr() % sal or \
+            (grouped and (st[0] % sal or (E > 1 and st[0] < N * st[1]))):
+        raise ValueError(f"w_scale needs unit inner stride, {sal}-byte-aligned rows of at "
+                         f"least K / 32 bytes and a {sal}-byte-aligned base (strides {st})")
+    if max(E, 1) * N * st[-2] >= 2 ** 31:
+        raise ValueError("w_scale spans 2 GiB or more")
+
+
 def _check_skinny_a16(a, w, offsets=None, out=None, *, w_scale=None, out_dtype=None,
                       act: str = "none", ksplit="auto", workspace=None, grouped: bool = False,
                       glu: bool = False):
@@ -1321,40 +1370,10 @@ def _check_skinny_a16(a, w, offsets=None, out=None, *, w_scale=None, out_dtype=N
     if K < 1 or K % kmod:
         raise ValueError(f"{what} needs K % {kmod} == 0 for {w.dtype} weights (K = {K})")
     if grouped:
-        if not 1 <= E <= MAX_GROUPS:
-            raise ValueError(f"{what} takes 1 .. {MAX_GROUPS} groups, not {E}")
-        _check_offsets_dtype(offsets)
-        if offsets.dim() != 1 or offsets.shape[0] != E + 1 or not offsets.is_contiguous():
-            raise ValueError(f"offsets must be contiguous with shape ({E + 1},) for {E} groups, "
-                             f"not {tuple(offsets.shape)}")
-        if offsets.device != a.device:
-            raise ValueError(f"offsets is on {offsets.device}, the operands on {a.device}")
-        if E > 1 and w.stride(0) < N * w.stride(1):
-            raise ValueError(f"w needs experts at least N rows apart (strides "
-                             f"{tuple(w.stride())})")
-        if w.stride(0) * w.element_size() % 16:
-            raise ValueError("the experts' weights must be a multiple of 16 bytes apart")
-    for name, t in (("a", a), ("w", w)):
-        if t.stride(-1) != 1 or t.stride(-2) < t.shape[-1]:
-            raise ValueError(f"{name} needs unit inner stride and rows of at least K (strides "
-                             f"{tuple(t.stride())})")
-        if t.data_ptr() % 16 or t.stride(-2) * t.element_size() % 16:
-            raise ValueError(f"{what} needs 16-byte-aligned rows of {name}")
+        _check_group_layout(what, a, w, offsets, E, N)
+    _check_operand_rows(what, a, w)
     if sal:
-        shape = ((E,) if grouped else ()) + (N, K // 32)
-        if not isinstance(w_scale, torch.Tensor) or w_scale.dtype != torch.uint8:
-            raise TypeError("w_scale must be a uint8 tensor of E8M0 bytes")
-        if w_scale.device != a.device:
-            raise ValueError(f"w_scale is on {w_scale.device}, the operands on {a.device}")
-        if tuple(w_scale.shape) != shape:
-            raise ValueError(f"w_scale must have shape {shape}, not {tuple(w_scale.shape)}")
-        st = w_scale.stride()
-        if st[-1] != 1 or st[-2] % sal or st[-2] < K // 32 or w_scale.data_ptr() % sal or \
-                (grouped and (st[0] % sal or (E > 1 and st[0] < N * st[1]))):
-            raise ValueError(f"w_scale needs unit inner stride, {sal}-byte-aligned rows of at "
-                             f"least K / 32 bytes and a {sal}-byte-aligned base (strides {st})")
-        if max(E, 1) * N * st[-2] >= 2 ** 31:
-            raise ValueError("w_scale spans 2 GiB or more")
+        _check_a16_w_scale(a, w_scale, E, N, K, sal, grouped)
     cols = N // 2 if glu else N
     if glu and N % (2 * GLU_GROUP):
         raise ValueError(f"{what} with glu=True needs N % {2 * GLU_GROUP} == 0 (N = {N})")
@@ -1500,19 +1519,7 @@ def _check_w4a8(a, w, offsets=None, out=None, *, a_scale=None, w_scale=None, out
         raise ValueError(f"{what} needs N >= 1")
     _check_32_bits(M, N, K)
     if grouped:
-        if not 1 <= E <= MAX_GROUPS:
-            raise ValueError(f"{what} takes 1 .. {MAX_GROUPS} groups, not {E}")
-        _check_offsets_dtype(offsets)
-        if offsets.dim() != 1 or offsets.shape[0] != E + 1 or not offsets.is_contiguous():
-            raise ValueError(f"offsets must be contiguous with shape ({E + 1},) for {E} groups, "
-                             f"not {tuple(offsets.shape)}")
-        if offsets.device != a.device:
-            raise ValueError(f"offsets is on {offsets.device}, the operands on {a.device}")
-        if E > 1 and w.stride(0) < N * w.stride(1):
-            raise ValueError(f"w needs experts at least N rows apart (strides "
-                             f"{tuple(w.stride())})")
-        if w.stride(0) % 16:
-            raise ValueError("the experts' weights must be a multiple of 16 bytes apart")
+        _check_group_layout(what, a, w, offsets, E, N)
         if not isinstance(w_scale, torch.Tensor) or w_scale.dim() != 3:
             raise ValueError(f"w_scale must have shape {(E, N, K // 32)}, not "
                              f"{tuple(getattr(w_scale, 'shape', ()))}")
@@ -1521,12 +1528,7 @@ def _check_w4a8(a, w, offsets=None, out=None, *, a_scale=None, w_scale=None, out
                              f"apart (strides {tuple(w_scale.stride())})")
         if (M // 128 + E) * (-(-N // 128)) >= 2 ** 31:
             raise ValueError(f"{what}: the grid bound does not fit 32 bits")
-    for name, t in (("a", a), ("w", w)):
-        if t.stride(-1) != 1 or t.stride(-2) < t.shape[-1]:
-            raise ValueError(f"{name} needs unit inner stride and rows of at least K (strides "
-                             f"{tuple(t.stride())})")
-        if t.data_ptr() % 16 or t.stride(-2) * t.element_size() % 16:
-            raise ValueError(f"{what} needs 16-byte-aligned rows of {name}")
+    _check_operand_rows(what, a, w)
     # tile, K % 256 and the scale layout, per expert slice
     for g in sorted({0, E - 1}) if grouped else (None,):
         _check_block_scaled(_MX_W4A8_TILED, a, w if g is None else w[g], a_scale,
@@ -1616,3 +1618,131 @@ def gemm_w4a8_grouped(a, w, offsets, out=None, *, a_scale, w_scale, out_dtype=No
                     grouped=True)
     return _run_w4a8(t, a, w, offsets, out, a_scale, w_scale, tile, act, glu, out_quant,
                      out_scale, stream)
+
+
+# ---------------------------------------------------------------- tiled A16 GEMM (prefill shapes)
+# bf16 / f16 a on MXFP4 / MX-fp8 w on a tiled kernel of its own (csrc/gemm/gemm_a16_kernels.h). A
+# K-tile is 128 elements for both weight forms, so w_scale is read one 32-bit word per row and
+# K-tile: 4-byte alignment for MXFP4 too (the skinny kernel reads its fp4 scales 8 bytes at a time).
+A16_TILES = ("128x128", "256x128")  # gemm_a16.h a16_offers()
+_A16_TILED_SCALE_ALIGN = 4
+
+
+def _check_a16(a, w, offsets=None, out=None, *, w_scale=None, out_dtype=None, tile: str = "auto",
+               act: str = "none", glu: bool = False, grouped: bool = False):
+    """Every refusal of :func:`gemm_a16` / :func:`gemm_a16_grouped`, on the host and before
+    anything is loaded or launched (CPU tensors pass through it; the offsets' content is never
+    read). Returns ``(M, N, K, E, output dtype)``: ``K`` in elements, ``N`` the rows of ``w`` (the
+    output has ``N / 2`` columns with ``glu``), ``E = 0`` for the dense form."""
+    import torch
+
+    what = "the grouped A16 GEMM" if grouped else "the A16 GEMM"
+    if act not in ACTS:
+        raise ValueError(f"unknown activation {act!r}")
+    wd = 3 if grouped else 2
+    if not isinstance(a, torch.Tensor) or not isinstance(w, torch.Tensor) or a.dim() != 2 \
+            or w.dim() != wd:
+        raise ValueError(f"{what} takes a as [M, K] and w as "
+                         f"{'[E, N, K]' if grouped else '[N, K]'}, not "
+                         f"{tuple(getattr(a, 'shape', ()))} and {tuple(getattr(w, 'shape', ()))}")
+    if a.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"{what} takes bf16 or f16 activations, not {a.dtype} (MX-fp8 "
+                        "activations on MXFP4 weights: gemm_w4a8)")
+    if not _is_fp4(w) and w.dtype != torch.float8_e4m3fn:
+        raise TypeError(f"{what} takes w as float4_e2m1fn_x2 or float8_e4m3fn under w_scale, not "
+                        f"{w.dtype}: 16-bit weights stay with gemm (decode shapes: "
+                        "gemm_skinny_a16)")
+    form = "mxfp4" if _is_fp4(w) else "mx"
+    kmod = _A16_FORMS[form][0]
+    M, N, K = a.shape[0], w.shape[-2], a.shape[1]
+    if K != (2 if form == "mxfp4" else 1) * w.shape[-1]:
+        raise ValueError(f"K mismatch: A {tuple(a.shape)} vs W {tuple(w.shape)}"
+                         f"{' (two elements per byte)' if form == 'mxfp4' else ''}")
+    if w_scale is None:
+        raise ValueError(f"{what} needs w_scale (w is {w.dtype})")
+    if w.device != a.device:
+        raise ValueError("operands on different devices")
+    E = w.shape[0] if grouped else 0
+    if N < 1:
+        raise ValueError(f"{what} needs N >= 1")
+    _check_32_bits(M, N, K)
+    if K < 1 or K % kmod:
+        raise ValueError(f"{what} needs K % {kmod} == 0 for {w.dtype} weights (K = {K})")
+    _check_tile(what, tile, tiles=A16_TILES)
+    if grouped:
+        _check_group_layout(what, a, w, offsets, E, N)
+        if (M // 128 + E) * (-(-N // 128)) >= 2 ** 31:
+            raise ValueError(f"{what}: the grid bound does not fit 32 bits")
+    _check_operand_rows(what, a, w)
+    _check_a16_w_scale(a, w_scale, E, N, K, _A16_TILED_SCALE_ALIGN, grouped)
+    cols = N // 2 if glu else N
+    if glu and N % (2 * GLU_GROUP):
+        raise ValueError(f"{what} with glu=True needs N % {2 * GLU_GROUP} == 0 (N = {N})")
+    odt = _check_dense_out(what, a, out, out_dtype, (a.dtype, torch.float32), M, cols)
+    return M, N, K, E, odt
+
+
+def _run_a16(t, a, w, offsets, out, w_scale, tile, act, glu, stream):
+    """The launch of both A16 forms, after every refusal of :func:`_check_a16` (``t``)."""
+    import torch
+
+    M, N, K, E, odt = t
+    C = load()
+    if a.device.type != "cuda":
+        raise ValueError("native GEMM operands must be ROCm device tensors")
+    if out is None:
+        out = torch.empty((M, N // 2 if glu else N), dtype=odt, device=a.device)
+    fp4 = _is_fp4(w)
+    wm = 2 if fp4 else 1
+    s = _stream(stream, a)
+    C.gemm_a16(
+        a=a.data_ptr(), w=w.data_ptr(), c=out.data_ptr(), lda=a.stride(0), ldw=wm * w.stride(-2),
+        ldc=out.stride(0), M=M, N=N, K=K, din=dtype_code(a.dtype), dout=dtype_code(odt),
+        dw=DT_FP4 if fp4 else DT_FP8, tile=TILES[tile], w_scale=w_scale.data_ptr(),
+        w_scale_ld=w_scale.stride(-2), act=ACTS[act], glu=int(bool(glu)),
+        offs=offsets.data_ptr() if E else 0, ngroups=E, w_gstride=wm * w.stride(0) if E else 0,
+        w_scale_gstride=w_scale.stride(0) if E else 0, stream=s)
+    if stream is not None:  # what was allocated here stays allocated until that stream is done
+        out.record_stream(torch.cuda.ExternalStream(s))
+    return out
+
+
+def gemm_a16(a, w, out=None, *, w_scale, out_dtype=None, tile: str = "auto", act: str = "none",
+             glu: bool = False, stream=None):
+    """``out = act(a @ w.T)`` for bf16 / f16 ``a [M, K]`` that is not quantised on MX weights at
+    prefill shapes, any ``M``, on the tiled A16 kernel (``csrc/gemm/gemm_a16_kernels.h``).
+    ``w [N, K]`` is one of
+
+    * MXFP4, ``float4_e2m1fn_x2 [N, K / 2]``, ``K % 256 == 0``: W4A16;
+    * MX-fp8, ``float8_e4m3fn [N, K]``, ``K % 128 == 0``: W8A16;
+
+    with E8M0 ``w_scale [N, K / 32]`` (4-byte aligned); operand rows 16-byte aligned. 16-bit
+    weights are refused: they stay with :func:`gemm`. The weight bytes travel packed into LDS and
+    are expanded in registers in front of the 16-bit MFMA. The numerics are
+    :func:`gemm_skinny_a16`'s: the value multiplied is ``e * 2^(s - 127)`` in ``a``'s dtype, exact
+    whenever that is zero or a normal number of the dtype (outside that range the result is the
+    conversion instruction's and not specified), f32 sums, one rounding. A scale byte 255 makes
+    exactly that weight row's output column NaN, an e4m3 NaN byte too; NaN / Inf in ``a`` reach
+    their output row. The decode sibling is :func:`gemm_skinny_a16` (``M <= 64``).
+
+    Output ``a``'s dtype (default) or f32 on any row pitch, any ``N >= 1``; there is no quantised
+    output. ``tile``: ``"auto"`` (gemm_a16.h ``a16_auto_tile``) or one of :data:`A16_TILES`. ``act``
+    applies to the f32 sum before the one rounding. ``glu=True``: ``w`` is the :func:`pack_glu`
+    weight, ``N % 64 == 0``, and the output has ``N / 2`` columns, ``act(gate) * up`` in f32
+    (:func:`glu_reference`). :func:`_check_a16` holds every refusal."""
+    t = _check_a16(a, w, None, out, w_scale=w_scale, out_dtype=out_dtype, tile=tile, act=act,
+                   glu=glu)
+    return _run_a16(t, a, w, None, out, w_scale, tile, act, glu, stream)
+
+
+def gemm_a16_grouped(a, w, offsets, out=None, *, w_scale, out_dtype=None, tile: str = "auto",
+                     act: str = "none", glu: bool = False, stream=None):
+    """:func:`gemm_a16` over per-expert weights in one launch (MoE prefill): rows
+    ``[o'[g], o'[g + 1])`` of ``a [T, K]`` times ``w[g]`` of ``w [E, N, K]`` under
+    ``w_scale [E, N, K / 32]``. ``offsets`` is the int32 ``[E + 1]`` device tensor of
+    :func:`gemm_grouped`, read and clamped by the kernel only (:func:`clamp_offsets`; no host
+    sync); empty groups are legal, rows outside ``[o'[0], o'[E])`` are not written, and a group's
+    rows are bit for bit what :func:`gemm_a16` writes for them with the same tile code."""
+    t = _check_a16(a, w, offsets, out, w_scale=w_scale, out_dtype=out_dtype, tile=tile, act=act,
+                   glu=glu, grouped=True)
+    return _run_a16(t, a, w, offsets, out, w_scale, tile, act, glu, stream)
